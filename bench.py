@@ -2,7 +2,8 @@
 """Headline benchmark: labeled+unlabeled images/sec/node of one step of the reference's drivers on the MI355X hot path, synthetic data.
 
     python bench.py [--workload mt|sup|hpfg|cps|ctct] [--gpus N] [--steps K] [--warmup W] [--math bf16x3|f32] [--no-graph]
-                    [--local-bn] [--no-overlap] [--rccl] [--no-cpu-baseline] [--no-f32-line] [--no-probe]
+                    [--local-bn] [--no-overlap] [--rccl] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-f32-line] [--no-probe]]
 
 Workloads = BASELINE.json configs (the default, `mt`, is configs[1], the one the metric is quoted on):
   sup   configs[0]  sup_ACDC.py:83-93                          U-Net 1->4, 8 x 224^2, SGD + cosine schedule
@@ -17,19 +18,24 @@ file as a CHILD process (before anything here touches the GPU) and relays its JS
 one rank of the job.  One rank per GPU (process group over RCCL), weak scaling (per-GPU batch fixed).  N > 1 runs the mode BASELINE.json's
 north_star names: gradients AND BatchNorm / loss sums cross the ranks (R ranks == one process on the global batch; the sums through peer
 mailboxes inside the finalize kernels), the gradient exchange bucketed and overlapped with the encoder half of backward, everything through
-IPC-mapped peer windows over xGMI inside the step's hipGraph (after a self-test on the node; `--rccl`: RCCL all-reduces between graphs).  The
-same job then times the DistributedDataParallel-semantics mode (per-rank BatchNorm, averaged gradients: `--local-bn` makes it the headline)
-and reports it beside the headline as `other_bn_mode`.
+IPC-mapped peer windows over xGMI inside the step's hipGraph (after a self-test on the node; `--rccl`: RCCL all-reduces between graphs).  With
+`--full` the same job then times the DistributedDataParallel-semantics mode (per-rank BatchNorm, averaged gradients: `--local-bn` makes it the
+headline) and reports it beside the headline as `other_bn_mode`.
+
+A plain run sets up, warms up, times the K steps once and prints the line; `--dump-outputs DIR` then also writes what the timed path computed
+in its last timed step (the step's returned tensors and every network's state, float32 / float64 .npy; at most 64 MB, larger arrays as a
+fixed seeded sample) -- the inputs and initial weights are seeded, so two builds compare output for output.  The fields marked --full
+below are measured only with `--full` and are null in a plain run.
 
 Prints ONE JSON line (rank 0): the driver's contract plus
   step_roofline   the whole step against its algorithmic bytes / FLOPs,
-  roofline        the kernel family with the largest share of the step's kernel time, measured live: every conv / dgrad / wgrad /
+  roofline        --full: the kernel family with the largest share of the step's kernel time, measured live: every conv / dgrad / wgrad /
                   BatchNorm launch of the U-Net engines is bracketed by device time stamps (one-wave kernels storing s_memrealtime) inside
                   a second captured hipGraph of the same step -- no host events, no eager steps -- and the families' times are summed per
-                  step; `longest_launch` is kept beside it,
-  blocks          the contract's K timed steps are block 0; four more blocks of K steps follow: ms/step of each, median, min, max,
-  f32_math        the same step with exact-fp32 MFMA products (N = 1, `mt` only),
-  cpu_baseline    the CPU oracle of the same step on this host's cores (bounded sample; all physical cores),
+                  step; `longest_launch` is kept beside it (a plain run reports the whole step here instead),
+  blocks          the contract's K timed steps are block 0; with --full four more blocks of K steps follow: ms/step of each, median, min, max,
+  f32_math        --full: the same step with exact-fp32 MFMA products (N = 1, `mt` only),
+  cpu_baseline    --full: the CPU oracle of the same step on this host's cores (bounded sample; all physical cores),
   exchange_path   N > 1: what every rank's sums actually travelled through (peer windows / mailboxes or the RCCL fallback and why), its
                   window mapping and self-test results and its peer error word.
 """
@@ -82,9 +88,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="mt", choices=["mt", "sup", "hpfg", "cps", "ctct"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-line", action="store_true", help="skip the secondary exact-fp32 measurement")
-    ap.add_argument("--no-probe", action="store_true", help="skip the per-kernel time stamps (roofline = step figures only)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: four further timed blocks, the per-kernel "
+                    "probe (roofline), the exact-fp32 line, the CPU baseline and (N > 1) the other BatchNorm mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (rank 0; float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-f32-line", action="store_true", help="--full: skip the secondary exact-fp32 measurement")
+    ap.add_argument("--no-probe", action="store_true", help="--full: skip the per-kernel time stamps (roofline = step figures only)")
     ap.add_argument("--math", default=os.environ.get("HPFG_MATH", "bf16x3"), choices=["bf16x3", "f32"])
     ap.add_argument("--lab", type=int, default=None, help="labelled images per GPU (default: the workload's BASELINE figure)")
     ap.add_argument("--unlab", type=int, default=None)
@@ -96,12 +106,18 @@ def parse():
     ap.add_argument("--overlap", action="store_true", help="(the default for N > 1) bucketed gradient exchange overlapped with the encoder half of backward "
                     "(peer windows: inside the one graph; --rccl: a chain of hipGraphs around eager RCCL calls)")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: ONE gradient exchange after backward instead")
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps (block 0 is the contract's measurement)")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps steps (block 0 is the contract's measurement; default 1, "
+                    "5 with --full)")
     ap.add_argument("--rccl", action="store_true", help="N > 1: the gradient all-reduce as an RCCL call between two hipGraphs instead of the peer-window "
                     "exchange captured inside the step's one graph (the fallback bench.py takes by itself when the peer windows fail their self-test)")
     ap.add_argument("--no-p2p", action="store_true", help="--sync-bn: exchange the BatchNorm / loss sums with host-launched RCCL all-reduces (eager step) instead "
                     "of the peer mailboxes the finalize kernels write themselves (hipIpc over xGMI; the step stays a chain of hipGraphs)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.blocks is None:
+        a.blocks = 5 if a.full else 1
+    return a
 
 
 def relaunch(a):
@@ -232,7 +248,8 @@ class Workload:
 
 def timed_run(wl, dp, use_graph, steps, warmup, dev, blocks=1):
     """W untimed + K timed steps bracketed by barrier + synchronize; returns (seconds, graph actually used, last iteration, [seconds of every
-    block]): block 0 is the contract's measurement, `blocks - 1` further blocks of K steps are timed the same way (spread of the figure)."""
+    block], what the last step returned): block 0 is the contract's measurement, `blocks - 1` further blocks of K steps are timed the same
+    way (spread of the figure)."""
     import torch
     from hpfg_amd.train import GraphedStep
     step, inputs = wl.step, wl.inputs
@@ -249,9 +266,8 @@ def timed_run(wl, dp, use_graph, steps, warmup, dev, blocks=1):
 
     def one(i):
         if runner is not None:
-            runner.step(list(inputs), i)
-        else:
-            step.step(*inputs, i)
+            return runner.step(list(inputs), i)
+        return step.step(*inputs, i)
 
     def barrier():
         if dp is not None:
@@ -262,12 +278,12 @@ def timed_run(wl, dp, use_graph, steps, warmup, dev, blocks=1):
         it += 1
         one(it)
     barrier()
-    dts = []
+    dts, last = [], None
     for _ in range(max(1, blocks)):
         t0 = time.perf_counter()
         for _ in range(steps):
             it += 1
-            one(it)
+            last = one(it)
         barrier()
         dt = time.perf_counter() - t0
         if dp is not None:
@@ -280,7 +296,50 @@ def timed_run(wl, dp, use_graph, steps, warmup, dev, blocks=1):
         except RuntimeError as e:
             print(f"[bench] rank {dp.rank}: {e}", file=sys.stderr, flush=True)
             raise SystemExit(3)
-    return dts[0], use_graph, it, dts
+    return dts[0], use_graph, it, dts, last
+
+
+# ---- output dump -----------------------------------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, wl, last):
+    """What the timed path computed in its last step, as a caller receives it: the tensors the step returned (`step.<key>`) and every
+    network's state_dict after the step's update (`model<i>.<key>`), one float32 / float64 .npy each.  If the whole exceeds 64 MB, the
+    largest arrays are cut down to a fixed seeded sample of their elements (the same indices in every run), so that the total fits."""
+    import zlib
+
+    import numpy as np
+    import torch
+    arrays = {}
+    for k, v in (last or {}).items():
+        if torch.is_tensor(v):
+            arrays[f"step.{k}"] = v
+    for i, m in enumerate(wl.models):
+        for k, v in m.state_dict().items():
+            arrays[f"model{i}.{k}"] = v
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        host[k] = v.to("cpu", torch.float64 if v.dtype in (torch.float64, torch.int64) else torch.float32).numpy()
+    # fit the budget: from the smallest array up, each keeps its elements up to an equal share of what is left
+    left, n_left, sampled = DUMP_MAX_BYTES, len(host), []
+    for k in sorted(host, key=lambda k: host[k].nbytes):
+        a = host[k]
+        share = left // n_left
+        if a.nbytes > share:
+            keep = max(1, share // a.itemsize)
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, keep, replace=False))
+            host[k] = a.reshape(-1)[idx]
+            sampled.append(k)
+        left -= host[k].nbytes
+        n_left -= 1
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    total = sum(a.nbytes for a in host.values())
+    print(f"[bench] wrote {len(host)} arrays ({total / 1e6:.1f} MB) to {out_dir}" +
+          (f"; seeded samples of {', '.join(sampled)}" if sampled else ""), file=sys.stderr)
 
 
 # ---- per-kernel probe ------------------------------------------------------------------------------------------------------------------
@@ -646,7 +705,10 @@ def main():
     # all-gathers the neck features with a host-launched collective), the global-batch mode runs eager.
     sync_mode = dp is not None and dp.sync_bn and (world > 1 or a.force_sync)
     use_graph = (not a.no_graph) and (not sync_mode or (dp.p2p and (a.workload != "hpfg" or dp.p2p_grads)))
-    dt, use_graph, it, dts = timed_run(wl, dp, use_graph, a.steps, a.warmup, dev, blocks=a.blocks)
+    dt, use_graph, it, dts, last = timed_run(wl, dp, use_graph, a.steps, a.warmup, dev, blocks=a.blocks)
+    if a.dump_outputs and rank == 0:      # before anything below steps these networks again
+        dump_outputs(a.dump_outputs, wl, last)
+    del last
     ms = dt / a.steps * 1e3
     value = wl.n_img * world / (dt / a.steps)
     bl = sorted(d / a.steps * 1e3 for d in dts)
@@ -655,7 +717,7 @@ def main():
     headline_sync = bool(dp is not None and dp.sync_bn)
 
     other = None
-    if dp is not None and world > 1:
+    if a.full and dp is not None and world > 1:
         # the other BatchNorm mode on the same ranks (fresh models and step objects): DistributedDataParallel semantics when the headline is
         # the global-batch mode, and vice versa
         dp.sync_bn = not headline_sync
@@ -666,7 +728,7 @@ def main():
             sync2 = dp.sync_bn
             ug2 = (not a.no_graph) and (not sync2 or (dp.p2p and (a.workload != "hpfg" or dp.p2p_grads)))
             k2 = max(5, a.steps // 2)
-            dt2, ug2, _, _ = timed_run(wl2, dp, ug2, k2, max(3, a.warmup // 2), dev)
+            dt2, ug2, *_ = timed_run(wl2, dp, ug2, k2, max(3, a.warmup // 2), dev)
             other = {"sync_bn": bool(sync2), "value": round(wl2.n_img * world / (dt2 / k2), 2), "unit": "images/s", "ms_per_step": round(dt2 / k2 * 1e3, 4),
                      "steps": k2, "hipgraph": bool(ug2),
                      "mode": "global-batch equivalence (BatchNorm + loss sums exchanged)" if sync2 else "per-rank BatchNorm, gradients averaged (DDP semantics)"}
@@ -678,7 +740,7 @@ def main():
     if dp is not None:          # every rank's exchange path + peer error word (collective: all ranks call it), for the line rank 0 prints
         xpath = dp.exchange_report(rccl_requested=a.rccl)
     roof = f32 = cpu = None
-    if rank == 0 and not a.no_probe and use_graph:
+    if a.full and rank == 0 and not a.no_probe and use_graph:
         pw = wl
         if dp is not None:      # the per-rank work is the same at every N (weak scaling): probe a private copy of the step without a process group
             pw = Workload(a.workload, a, dev, a.math, None, rank)
@@ -690,15 +752,15 @@ def main():
             print(f"[bench] per-kernel probe failed ({type(e).__name__}: {e})", file=sys.stderr)
         if pw is not wl:
             del pw
-    if world == 1 and dp is None and not a.no_f32_line and a.math != "f32" and a.workload == "mt":
+    if a.full and world == 1 and dp is None and not a.no_f32_line and a.math != "f32" and a.workload == "mt":
         del wl
         torch.cuda.empty_cache()
         wl = Workload(a.workload, a, dev, "f32", None, rank)
         k2 = max(5, a.steps // 2)
-        dt2, g2, _, _ = timed_run(wl, None, use_graph, k2, max(3, a.warmup // 2), dev)
+        dt2, g2, *_ = timed_run(wl, None, use_graph, k2, max(3, a.warmup // 2), dev)
         f32 = {"dtype": DTYPE["f32"], "value": round(wl.n_img / (dt2 / k2), 2), "unit": "images/s", "ms_per_step": round(dt2 / k2 * 1e3, 4), "steps": k2,
                "hipgraph": bool(g2), "note": "same step, HPFG_MATH=f32: every product exact fp32 (v_mfma_f32_16x16x4_f32); meets 1e-3 on every fixture"}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:      # reported baseline: rank 0 at N=1 only
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:      # reported baseline: rank 0 at N=1 only
         cpu = cpu_baseline(a.workload, wl.lab, wl.unlab, wl.size)
     if rank == 0:
         par = f"dp{world}"
