@@ -8,7 +8,7 @@
                     2021_12_MIDL_CTCT_ACDC.py (CTCT) and 2022_08_CVPR_S4CVNet_ACDC.py on the same kernels
 
 Each step object owns the optimizer(s) / scheduler(s) built by the reference-compatible factories and exposes
-``step(batch..., cur_itrs) -> dict of device scalars``.  Nothing in a step synchronises with the host: losses stay on the
+``step(batch..., cur_itrs) -> dict of device scalars``; ``_StepBase`` owns the shape of an iteration, a law adds its own arithmetic.  Nothing in a step synchronises with the host: losses stay on the
 device (the reference's ``loss.item()`` / per-class ``dice.item()`` calls have no counterpart); per-step scalars (learning rates,
 consistency weight, EMA alpha) are staged through one pinned buffer and read by the kernels from device memory, so a whole
 step can be captured into a hipGraph (``GraphedStep``).
@@ -17,7 +17,9 @@ The driver loops at the bottom keep the reference's function names and signature
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import math
 import os
 from typing import Dict, Optional
 
@@ -108,54 +110,123 @@ def cutmix_blend(a: torch.Tensor, b: torch.Tensor, mask: torch.Tensor) -> torch.
 
 
 class _StepBase:
-    def __init__(self, dev, dp=None):
-        self.dev, self.dp = dev, dp
-        self.sc = StepScalars(dev)
+    """The skeleton every step law shares.  ``trainable``: the one or two networks the step trains -- one is ``model``, with ``optimizer`` /
+    ``lr_scheduler`` built from ``args`` (its lr read from S_LR1); two are ``model1`` / ``model2``, with ``optimizer1/2`` / ``lr_scheduler1/2``
+    built from ``args.model1/2`` (S_LR1 / S_LR2).  ``ema_model``: the no-grad teacher, if the law has one.
+
+    One iteration = host_scalars -> sc.push() -> device_step -> after (``eager_step``; GraphedStep replays the device_step part), and
+    device_step = device_fwd_bwd -> exchange -> device_update.  A law writes host_scalars and device_fwd_bwd and overrides only what differs."""
+
+    def __init__(self, args, dp, trainable, ema_model=None):
+        self.dev = next(trainable[0].parameters()).device
+        self.dp, self.args = dp, args
+        self.sc = StepScalars(self.dev)
         if dp is not None:
             self.sc.on_push = lambda: setattr(dp, "_loss_call", 0)
         # HPFG_STEP_MARKS=1: timestamp kernels at phase boundaries of the step (tools/stream_timeline.py); off by default
-        self.marks = torch.zeros(32, dtype=torch.int64, device=dev) if os.environ.get("HPFG_STEP_MARKS", "0") == "1" else None
+        self.marks = torch.zeros(32, dtype=torch.int64, device=self.dev) if os.environ.get("HPFG_STEP_MARKS", "0") == "1" else None
         # the no-grad teacher forward is independent of the student forward: run it on a second HIP stream so that the two
         # kernel chains (and, data parallel, their small BatchNorm collectives) overlap; joins before the loss.
-        self.overlap = os.environ.get("HPFG_OVERLAP", "1") == "1"
-        self.side = torch.cuda.Stream(device=dev) if self.overlap else None
+        self.side = torch.cuda.Stream(device=self.dev)
+        self.side2 = None          # a third stream for the laws that fork a student as well (_side2: created at first use)
+        self.trainable = list(trainable)
+        self.models = self.trainable + ([ema_model] if ema_model is not None else [])      # every network of the step (GraphedStep)
+        for m in self.trainable:
+            self._attach(m, alone=len(self.trainable) == 1)
+        if ema_model is not None:
+            self.ema_model = ema_model
+            self._attach(ema_model)
+        self._build_optimizers()
+
+    def _build_optimizers(self):
+        two = len(self.trainable) == 2
+        names, sub = (("1", "2"), (self.args.model1, self.args.model2)) if two else (("",), (self.args,))
+        self.optimizers = [build_optimizer(args=a, model=m) for a, m in zip(sub, self.trainable)]
+        self.lr_schedulers = [build_lr_scheduler(args=a, optimizer=o) for a, o in zip(sub, self.optimizers)]
+        for n, m, o, s, lr_slot in zip(names, self.trainable, self.optimizers, self.lr_schedulers, (S_LR1, S_LR2)):
+            setattr(self, "model" + n, m)
+            setattr(self, "optimizer" + n, o)
+            setattr(self, "lr_scheduler" + n, s)
+            o._lr_dev = self.sc.view(lr_slot)
+        self._set_grad_scale(*self.optimizers)
+        self._own_gather(*self.optimizers)
+
+    def eager_step(self, inputs, cur_itrs, **kw):
+        """One iteration, launched eagerly; ``kw`` goes to host_scalars.  (``inputs`` is unpacked after the push: a generator of device
+        copies made there runs behind the scalars' copy.)"""
+        self.host_scalars(cur_itrs, **kw)
+        self.sc.push()
+        r = self.device_step(*inputs)
+        self.after()
+        return r
+
+    def device_step(self, *inputs):
+        r = self.device_fwd_bwd(*inputs)
+        self.exchange()
+        self.device_update()
+        return r
+
+    def exchange(self):
+        self._reduce_grads(*self.trainable)
+
+    def device_update(self):
+        for o in self.optimizers:
+            o.step(push_lr=False) if hasattr(o, "push_lr") else o.step()         # the fused optimizers read their lr from the device scalars
+
+    def after(self):
+        for s in self.lr_schedulers:
+            s.step()
+
+    def _cons_w(self, cur_itrs, cons_w=None, rampup=sigmoid_rampup):
+        """The consistency weight: ``consistency * rampup(cur_itrs // 150, consistency_rampup)`` unless the caller fixes it."""
+        a = self.args
+        return a.consistency * rampup(cur_itrs // 150, a.consistency_rampup) if cons_w is None else cons_w
 
     def _mark(self, i):
         if self.marks is not None:
             L.check(L.load().hpfg_timestamp(self.marks.data_ptr() + 8 * i, torch.cuda.current_stream(self.dev).cuda_stream), "timestamp")
 
-    def _teacher_forward(self, ema_model, x):
-        """ema_model(x) under no_grad, on the side stream when overlap is enabled.  Returns the teacher outputs."""
-        if not self.overlap:
-            with torch.no_grad():
-                return ema_model(x)
+    def _side2(self):
+        if self.side2 is None:
+            self.side2 = torch.cuda.Stream(device=self.dev)
+        return self.side2
+
+    @contextlib.contextmanager
+    def _fork(self, stream):
+        """Run the block on `stream`, behind everything queued so far on the current stream; ``_join(stream, ...)`` ends the fork.  A
+        network whose forward runs there back-propagates there too (autograd runs a node on the stream of its forward)."""
+        stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(stream):
+            yield
+
+    def _join(self, stream, *outs):
+        """The current stream waits for `stream`; the tensors in `outs` (nested one level in tuples / lists) made there are recorded as used
+        on the current stream.  Called with no outputs after a backward: a forked network's backward node hands autograd no gradient tensors
+        (they are written in place into the flat buffer), so autograd has nothing to synchronise that stream with -- the step joins it
+        explicitly before anything reads the gradients and, inside a capture, before the capture ends (an unjoined forked stream is what
+        made hipStreamEndCapture of the HPFG step fault)."""
         cur = torch.cuda.current_stream(self.dev)
-        self.side.wait_stream(cur)
-        with torch.cuda.stream(self.side), torch.no_grad():
+        cur.wait_stream(stream)
+        for o in outs:
+            for t_ in (o if isinstance(o, (tuple, list)) else (o,)):
+                for u in (t_ if isinstance(t_, (tuple, list)) else (t_,)):
+                    if torch.is_tensor(u):
+                        u.record_stream(cur)
+
+    def _teacher_forward(self, x):
+        """ema_model(x) under no_grad on the side stream; the caller joins it with ``_join(self.side, outputs)``."""
+        with self._fork(self.side), torch.no_grad():
             self._mark(2)
-            out = ema_model(x)
+            out = self.ema_model(x)
             self._mark(3)
-        self._pending_join = True
         return out
 
-    def _join_teacher(self, *outs):
-        if self.overlap and getattr(self, "_pending_join", False):
-            cur = torch.cuda.current_stream(self.dev)
-            cur.wait_stream(self.side)
-            for o in outs:
-                for t_ in (o if isinstance(o, (tuple, list)) else (o,)):
-                    for u in (t_ if isinstance(t_, (tuple, list)) else (t_,)):
-                        if torch.is_tensor(u):
-                            u.record_stream(cur)
-            self._pending_join = False
-
-    def _join_backward(self, stream):
-        """A network whose forward ran on `stream` back-propagates there too (autograd runs a node on the stream of its forward).  Its
-        backward node hands autograd no gradient tensors (they are written in place into the flat buffer), so autograd has nothing to
-        synchronise that stream with: the step joins it explicitly before anything reads the gradients -- and, inside a capture, before
-        the capture ends (an unjoined forked stream is what made hipStreamEndCapture of the HPFG step fault)."""
-        if stream is not None and self.overlap:
-            torch.cuda.current_stream(self.dev).wait_stream(stream)
+    def _backward(self, loss, stream):
+        """zero_grad + backward of the two students' summed loss, then the join of the student that ran on `stream`."""
+        for o in self.optimizers:
+            o.zero_grad()
+        loss.backward()
+        self._join(stream)
 
     def _attach(self, model, alone: bool = False):
         """alone: the only trainable network of the step -- its backward may fork its off-chain weight gradients onto a side stream
@@ -170,16 +241,6 @@ class _StepBase:
             model.defer_wgrad = True
         if any(p.requires_grad for p in model.parameters()):
             model.direct_grads = True          # one zero_grad + one backward per step: write gradients in place (no memset, no add)
-
-    def _sgd_ema_update(self):
-        """optimizer.step(); update_ema_variables(model, ema_model, ...) -- the tail of every Mean-Teacher-family iteration
-        (2017_03_NIPS_Mean-Teacher_ACDC.py:108-113) -- as ONE launch over the student's flat buffers where the optimizer offers it."""
-        fs, ft = getattr(self.model, "flat_params", None), getattr(self.ema_model, "flat_params", None)
-        if isinstance(self.optimizer, FusedSGD) and fs is not None and ft is not None and fs.numel() == ft.numel() and fs.is_cuda:
-            self.optimizer.step(push_lr=False, ema=(ft, fs.numel(), self.sc.view(S_ALPHA)))
-        else:
-            self.optimizer.step(push_lr=False)
-            update_ema_variables(self.model, self.ema_model, self.args.ema_decay, 0, alpha_dev=self.sc.view(S_ALPHA))
 
     def _loss_backward(self, res):
         """backward() of the fused loss vector [total, parts...]: only element 0 carries gradient; a constant one-hot gradient
@@ -238,14 +299,7 @@ class _StepBase:
 
 class SupervisedStep(_StepBase):
     def __init__(self, model, args, dp=None):
-        super().__init__(next(model.parameters()).device, dp)
-        self.model, self.args = model, args
-        self._attach(model, alone=True)
-        self.optimizer = build_optimizer(args=args, model=model)
-        self.lr_scheduler = build_lr_scheduler(args=args, optimizer=self.optimizer)
-        self.optimizer._lr_dev = self.sc.view(S_LR1)
-        self._set_grad_scale(self.optimizer)
-        self._own_gather(self.optimizer)
+        super().__init__(args, dp, [model])
         self.sc.host[S_COEF_A:S_COEF_A + 2] = torch.tensor([0.5, 0.5])
 
     def host_scalars(self, cur_itrs):
@@ -258,93 +312,72 @@ class SupervisedStep(_StepBase):
         self._loss_backward(res)
         return {"loss": res[0].detach(), "logits": out.detach(), "parts": res.detach()}
 
-    def exchange(self):
-        self._reduce_grads(self.model)
-
-    def device_update(self):
-        self.optimizer.step(push_lr=False)
-
-    def device_step(self, img, label):
-        r = self.device_fwd_bwd(img, label)
-        self.exchange()
-        self.device_update()
-        return r
-
-    def after(self):
-        self.lr_scheduler.step()
-
     def step(self, img, label, cur_itrs):
-        self.host_scalars(cur_itrs)
-        self.sc.push()
-        r = self.device_step(img, label)
-        self.after()
-        return r
+        return self.eager_step((img, label), cur_itrs)
 
 
-class MeanTeacherStep(_StepBase):
+class _TeacherStudentStep(_StepBase):
+    """One trained network and its EMA teacher (Mean Teacher, ICT, UAMT): their shared scalars and update."""
+
     def __init__(self, model, ema_model, args, dp=None):
-        super().__init__(next(model.parameters()).device, dp)
-        self.model, self.ema_model, self.args = model, ema_model, args
-        self._attach(model, alone=True)
-        self._attach(ema_model)
-        self.optimizer = build_optimizer(args=args, model=model)
-        self.lr_scheduler = build_lr_scheduler(args=args, optimizer=self.optimizer)
-        self.optimizer._lr_dev = self.sc.view(S_LR1)
-        self._set_grad_scale(self.optimizer)
-        self._own_gather(self.optimizer)
-        self.teacher_after = 7      # the teacher's launches enter the step behind this layer of the student's forward (see device_fwd_bwd)
+        super().__init__(args, dp, [model], ema_model)
 
     def host_scalars(self, cur_itrs, cons_w=None):
-        a = self.args
-        w = a.consistency * sigmoid_rampup(cur_itrs // 150, a.consistency_rampup) if cons_w is None else cons_w
+        w = self._cons_w(cur_itrs, cons_w)
         h = self.sc.host
         h[S_LR1] = self._lr(self.optimizer)
-        h[S_ALPHA] = ema_alpha(cur_itrs, a.ema_decay)
+        h[S_ALPHA] = ema_alpha(cur_itrs, self.args.ema_decay)
         h[S_COEF_A:S_COEF_A + 5] = torch.tensor([0.5, 0.5, 0.0, 0.0, w])
         return w
+
+    def device_update(self):
+        """optimizer.step(); update_ema_variables(model, ema_model, ...) -- the tail of every Mean-Teacher-family iteration
+        (2017_03_NIPS_Mean-Teacher_ACDC.py:108-113) -- as ONE launch over the student's flat buffers where the optimizer offers it."""
+        fs, ft = getattr(self.model, "flat_params", None), getattr(self.ema_model, "flat_params", None)
+        if isinstance(self.optimizer, FusedSGD) and fs is not None and ft is not None and fs.numel() == ft.numel() and fs.is_cuda:
+            self.optimizer.step(push_lr=False, ema=(ft, fs.numel(), self.sc.view(S_ALPHA)))
+        else:
+            self.optimizer.step(push_lr=False)
+            update_ema_variables(self.model, self.ema_model, self.args.ema_decay, 0, alpha_dev=self.sc.view(S_ALPHA))
+
+
+class MeanTeacherStep(_TeacherStudentStep):
+    def __init__(self, model, ema_model, args, dp=None):
+        super().__init__(model, ema_model, args, dp)
+        self.teacher_after = 7      # the teacher's launches enter the step behind this layer of the student's forward (see device_fwd_bwd)
 
     def device_fwd_bwd(self, label_img, target_label, unlabel_img):
         """Everything up to (not including) the gradient exchange."""
         nl = label_img.shape[0]
         x = cat_batch(label_img, unlabel_img)
         self._mark(0)
-        if self.overlap:
-            # A captured graph submits its nodes in creation order and the earlier-submitted network wins the CUs layer by layer: with the
-            # teacher captured first the student -- whose forward also stores the side tensors and is what the loss waits for -- started 120 us
-            # late and finished 130 - 170 us behind the teacher (in-graph stamps, tools/stream_timeline.py).  So the student's nodes come
-            # first and the teacher's enter behind its 8th layer, forked from an event recorded at the step's start (no data dependency on
-            # the student): both now end within ~30 us of each other, the loss starts ~60 us earlier (profiles/r04_schedule_experiments.txt).
-            cur = torch.cuda.current_stream(self.dev)
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            self._mark(1)
-            box = []
+        # A captured graph submits its nodes in creation order and the earlier-submitted network wins the CUs layer by layer: with the
+        # teacher captured first the student -- whose forward also stores the side tensors and is what the loss waits for -- started 120 us
+        # late and finished 130 - 170 us behind the teacher (in-graph stamps, tools/stream_timeline.py).  So the student's nodes come
+        # first and the teacher's enter behind its 8th layer, forked from an event recorded at the step's start (no data dependency on
+        # the student): both now end within ~30 us of each other, the loss starts ~60 us earlier (profiles/r04_schedule_experiments.txt).
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self._mark(1)
+        box = []
 
-            def teacher():
-                with torch.cuda.stream(self.side), torch.no_grad():
-                    self.side.wait_event(ev)
-                    self._mark(2)
-                    box.append(self.ema_model(x))
-                    self._mark(3)
+        def teacher():
+            with torch.cuda.stream(self.side), torch.no_grad():
+                self.side.wait_event(ev)
+                self._mark(2)
+                box.append(self.ema_model(x))
+                self._mark(3)
 
-            self.model._after_layer = (self.teacher_after, teacher)
-            try:
-                out = self.model(x)
-            finally:          # (a forward that raises must not leave the teacher closure behind for the model's next forward, e.g. an evaluation)
-                self.model._after_layer = None
-            if not box:
-                teacher()
-            t_out = box[0]
-            self._pending_join = True
-        else:
-            t_out = self._teacher_forward(self.ema_model, x)
-            self._mark(1)
+        self.model._after_layer = (self.teacher_after, teacher)
+        try:
             out = self.model(x)
+        finally:          # (a forward that raises must not leave the teacher closure behind for the model's next forward, e.g. an evaluation)
+            self.model._after_layer = None
+        if not box:
+            teacher()
+        t_out = box[0]
         self._mark(4)
-        self._join_teacher(t_out)
-        return self._loss_bwd(out, t_out, target_label, nl)
-
-    def _loss_bwd(self, out, t_out, target_label, nl):
+        self._join(self.side, t_out)
         self._mark(5)
         res = seg_loss(out, target_label, nl, coef=self.sc.view(S_COEF_A, 8), teacher_logits=t_out, dp=self.dp)
         self.optimizer.zero_grad()
@@ -352,28 +385,12 @@ class MeanTeacherStep(_StepBase):
         self._mark(6)
         return {"loss": res[0].detach(), "parts": res.detach(), "logits": out.detach(), "t_logits": t_out}
 
-    def exchange(self):
-        self._reduce_grads(self.model)
-
     def device_update(self):
-        self._sgd_ema_update()
+        super().device_update()
         self._mark(7)
 
-    def device_step(self, label_img, target_label, unlabel_img):
-        r = self.device_fwd_bwd(label_img, target_label, unlabel_img)
-        self.exchange()
-        self.device_update()
-        return r
-
-    def after(self):
-        self.lr_scheduler.step()
-
     def step(self, label_img, target_label, unlabel_img, cur_itrs, cons_w=None):
-        self.host_scalars(cur_itrs, cons_w)
-        self.sc.push()
-        r = self.device_step(label_img, target_label, unlabel_img)
-        self.after()
-        return r
+        return self.eager_step((label_img, target_label, unlabel_img), cur_itrs, cons_w=cons_w)
 
 
 def mix_samples(a: torch.Tensor, b: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
@@ -395,36 +412,16 @@ def softmax_mix(t0: torch.Tensor, t1: torch.Tensor, f: torch.Tensor) -> torch.Te
     return out.permute(0, 3, 1, 2)
 
 
-class ICTStep(_StepBase):
+class ICTStep(_TeacherStudentStep):
     """Interpolation consistency training (2022_02_ISBI_ICT-MedSeg_ACDC.py:110-143): the student sees
     [labelled ; mix(u0, u1)], the train-mode teacher sees u0 and u1 separately, and the consistency target is the same mix of the
-    two teacher softmaxes.  Recomposition of the hot-path kernels plus two per-sample mix kernels."""
-
-    def __init__(self, model, ema_model, args, dp=None):
-        super().__init__(next(model.parameters()).device, dp)
-        self.model, self.ema_model, self.args = model, ema_model, args
-        self._attach(model, alone=True)
-        self._attach(ema_model)
-        self.optimizer = build_optimizer(args=args, model=model)
-        self.lr_scheduler = build_lr_scheduler(args=args, optimizer=self.optimizer)
-        self.optimizer._lr_dev = self.sc.view(S_LR1)
-        self._set_grad_scale(self.optimizer)
-        self._own_gather(self.optimizer)
+    two teacher softmaxes.  Recomposition of the hot-path kernels plus two per-sample mix kernels.  (No device_fwd_bwd: under split data
+    parallel the step stays eager.)"""
 
     def draw_mix_factors(self, unlabel_bs: int, rng=None) -> torch.Tensor:
-        import numpy as np
         rng = np.random if rng is None else rng
         a = float(getattr(self.args, "ict_alpha", 0.2))
         return torch.tensor(rng.beta(a, a, size=(unlabel_bs // 2, 1, 1, 1)), dtype=torch.float)      # host draw, as the reference (:111)
-
-    def host_scalars(self, cur_itrs, cons_w=None):
-        a = self.args
-        w = a.consistency * sigmoid_rampup(cur_itrs // 150, a.consistency_rampup) if cons_w is None else cons_w
-        h = self.sc.host
-        h[S_LR1] = self._lr(self.optimizer)
-        h[S_ALPHA] = ema_alpha(cur_itrs, a.ema_decay)
-        h[S_COEF_A:S_COEF_A + 5] = torch.tensor([0.5, 0.5, 0.0, 0.0, w])
-        return w
 
     def device_step(self, label_img, target_label, unlabel_img, mix_factors):
         nl, nu = label_img.shape[0], unlabel_img.shape[0]
@@ -439,21 +436,14 @@ class ICTStep(_StepBase):
         res = seg_loss(out, target_label, nl, coef=self.sc.view(S_COEF_A, 8), teacher_prob=tp, dp=self.dp)
         self.optimizer.zero_grad()
         self._loss_backward(res)
-        self._reduce_grads(self.model)
-        self._sgd_ema_update()
+        self.exchange()
+        self.device_update()
         return {"loss": res[0].detach(), "parts": res.detach(), "logits": out.detach(), "t_prob": tp}
-
-    def after(self):
-        self.lr_scheduler.step()
 
     def step(self, label_img, target_label, unlabel_img, cur_itrs, mix_factors=None, cons_w=None):
         if mix_factors is None:
             mix_factors = self.draw_mix_factors(unlabel_img.shape[0])
-        self.host_scalars(cur_itrs, cons_w)
-        self.sc.push()
-        r = self.device_step(label_img, target_label, unlabel_img, mix_factors)
-        self.after()
-        return r
+        return self.eager_step((label_img, target_label, unlabel_img, mix_factors), cur_itrs, cons_w=cons_w)
 
 
 def noise_add(x: torch.Tensor, noise: torch.Tensor, scale: float = 0.1, lo: float = -0.2, hi: float = 0.2) -> torch.Tensor:
@@ -488,34 +478,18 @@ def uncertainty_mask(pred_blocks, n_images: int, threshold_dev: torch.Tensor, wa
     return (mask, unc) if want_uncertainty else mask
 
 
-class UAMTStep(_StepBase):
+class UAMTStep(_TeacherStudentStep):
     """Uncertainty-aware Mean Teacher (2019_07_MICCAI_Uncertainty_Aware_ACDC.py:110-170): student forward on
     [labelled ; unlabelled], one noisy teacher forward for the consistency target, T=8 further noisy teacher predictions
     (T/2 forwards of the doubled unlabelled batch, all in train mode like the reference), entropy of their mean softmax -> mask,
-    masked softmax-MSE + 0.5*(CE + Dice), SGD, EMA.  Recomposition of the hot-path kernels plus noise / entropy-mask kernels."""
+    masked softmax-MSE + 0.5*(CE + Dice), SGD, EMA.  Recomposition of the hot-path kernels plus noise / entropy-mask kernels.  (No
+    device_fwd_bwd: under split data parallel the step stays eager.)"""
 
     T = 8
 
-    def __init__(self, model, ema_model, args, dp=None):
-        super().__init__(next(model.parameters()).device, dp)
-        self.model, self.ema_model, self.args = model, ema_model, args
-        self._attach(model, alone=True)
-        self._attach(ema_model)
-        self.optimizer = build_optimizer(args=args, model=model)
-        self.lr_scheduler = build_lr_scheduler(args=args, optimizer=self.optimizer)
-        self.optimizer._lr_dev = self.sc.view(S_LR1)
-        self._set_grad_scale(self.optimizer)
-        self._own_gather(self.optimizer)
-
     def host_scalars(self, cur_itrs, cons_w=None):
-        import math
-        a = self.args
-        w = a.consistency * sigmoid_rampup(cur_itrs // 150, a.consistency_rampup) if cons_w is None else cons_w
-        h = self.sc.host
-        h[S_LR1] = self._lr(self.optimizer)
-        h[S_ALPHA] = ema_alpha(cur_itrs, a.ema_decay)
-        h[S_THRESH] = (0.75 + 0.25 * sigmoid_rampup(cur_itrs, a.total_itrs)) * math.log(2)          # :162
-        h[S_COEF_A:S_COEF_A + 5] = torch.tensor([0.5, 0.5, 0.0, 0.0, w])
+        w = super().host_scalars(cur_itrs, cons_w)
+        self.sc.host[S_THRESH] = (0.75 + 0.25 * sigmoid_rampup(cur_itrs, self.args.total_itrs)) * math.log(2)          # :162
         return w
 
     def draw_noise(self, unlabel_img):
@@ -534,40 +508,21 @@ class UAMTStep(_StepBase):
         res = seg_loss(out, target_label, nl, coef=self.sc.view(S_COEF_A, 8), teacher_logits=ema_out, cons_mask=mask, dp=self.dp)
         self.optimizer.zero_grad()
         self._loss_backward(res)
-        self._reduce_grads(self.model)
-        self._sgd_ema_update()
+        self.exchange()
+        self.device_update()
         return {"loss": res[0].detach(), "parts": res.detach(), "logits": out.detach(), "mask": mask, "t_logits": ema_out.detach()}
-
-    def after(self):
-        self.lr_scheduler.step()
 
     def step(self, label_img, target_label, unlabel_img, cur_itrs, noise=None, cons_w=None):
         n0, rest = self.draw_noise(unlabel_img) if noise is None else noise
-        self.host_scalars(cur_itrs, cons_w)
-        self.sc.push()
-        r = self.device_step(label_img, target_label, unlabel_img, n0, rest)
-        self.after()
-        return r
+        return self.eager_step((label_img, target_label, unlabel_img, n0, rest), cur_itrs, cons_w=cons_w)
 
 
 class CPSStep(_StepBase):
     def __init__(self, model1, model2, args, dp=None):
-        super().__init__(next(model1.parameters()).device, dp)
-        self.model1, self.model2, self.args = model1, model2, args
-        self._attach(model1)
-        self._attach(model2)
-        self.optimizer1 = build_optimizer(args=args.model1, model=model1)
-        self.optimizer2 = build_optimizer(args=args.model2, model=model2)
-        self.lr_scheduler1 = build_lr_scheduler(args=args.model1, optimizer=self.optimizer1)
-        self.lr_scheduler2 = build_lr_scheduler(args=args.model2, optimizer=self.optimizer2)
-        self.optimizer1._lr_dev = self.sc.view(S_LR1)
-        self.optimizer2._lr_dev = self.sc.view(S_LR2)
-        self._set_grad_scale(self.optimizer1, self.optimizer2)
-        self._own_gather(self.optimizer1, self.optimizer2)
+        super().__init__(args, dp, [model1, model2])
 
     def host_scalars(self, cur_itrs, cons_w=None):
-        a = self.args
-        w = a.consistency * sigmoid_rampup(cur_itrs // 150, a.consistency_rampup) if cons_w is None else cons_w
+        w = self._cons_w(cur_itrs, cons_w)
         h = self.sc.host
         h[S_LR1], h[S_LR2] = self._lr(self.optimizer1), self._lr(self.optimizer2)
         h[S_COEF_A:S_COEF_A + 5] = torch.tensor([0.5, 0.5, 0.5 * w, 0.5 * w, 0.0])
@@ -577,71 +532,29 @@ class CPSStep(_StepBase):
         """Everything up to (not including) the gradient exchange."""
         nl = label_img.shape[0]
         x = cat_batch(label_img, unlabel_img)
-        if self.overlap:
-            # the two students are independent until the losses: the second one's forward runs on the side stream, and autograd runs its
-            # backward there too (a backward node executes on the stream of its forward), so both chains of small kernels overlap
-            cur = torch.cuda.current_stream(self.dev)
-            self.side.wait_stream(cur)
-            with torch.cuda.stream(self.side):
-                o2 = self.model2(x)
-            o1 = self.model1(x)
-            cur.wait_stream(self.side)
-            o2.record_stream(cur)
-        else:
-            o1 = self.model1(x)
+        # the two students are independent until the losses: the second one's forward -- and so its backward -- runs on the side stream,
+        # so both chains of small kernels overlap
+        with self._fork(self.side):
             o2 = self.model2(x)
+        o1 = self.model1(x)
+        self._join(self.side, o2)
         p1 = argmax_labels(o1[nl:])
         p2 = argmax_labels(o2[nl:])
         coef = self.sc.view(S_COEF_A, 8)
         r1 = seg_loss(o1, target_label, nl, coef=coef, pseudo=p2, dp=self.dp)
         r2 = seg_loss(o2, target_label, nl, coef=coef, pseudo=p1, dp=self.dp)
         loss = r1[0] + r2[0]
-        self.optimizer1.zero_grad()
-        self.optimizer2.zero_grad()
-        loss.backward()
-        self._join_backward(self.side)
+        self._backward(loss, self.side)
         return {"loss": loss.detach(), "parts1": r1.detach(), "parts2": r2.detach(), "logits1": o1.detach(), "logits2": o2.detach()}
 
-    def exchange(self):
-        self._reduce_grads(self.model1, self.model2)
-
-    def device_update(self):
-        for o in (self.optimizer1, self.optimizer2):
-            o.step(push_lr=False) if hasattr(o, "push_lr") else o.step()         # FusedSGD reads its lr from the device scalars
-
-    def device_step(self, label_img, target_label, unlabel_img):
-        r = self.device_fwd_bwd(label_img, target_label, unlabel_img)
-        self.exchange()
-        self.device_update()
-        return r
-
-    def after(self):
-        self.lr_scheduler1.step()
-        self.lr_scheduler2.step()
-
     def step(self, label_img, target_label, unlabel_img, cur_itrs, cons_w=None):
-        self.host_scalars(cur_itrs, cons_w)
-        self.sc.push()
-        r = self.device_step(label_img, target_label, unlabel_img)
-        self.after()
-        return r
+        return self.eager_step((label_img, target_label, unlabel_img), cur_itrs, cons_w=cons_w)
 
 
 class HPFGStep(_StepBase):
     def __init__(self, model1, model2, ema_model, args, dp=None):
         from .utils import Dense_Loss
-        super().__init__(next(model1.parameters()).device, dp)
-        self.model1, self.model2, self.ema_model, self.args = model1, model2, ema_model, args
-        for m in (model1, model2, ema_model):
-            self._attach(m)
-        self.optimizer1 = build_optimizer(args=args.model1, model=model1)
-        self.optimizer2 = build_optimizer(args=args.model2, model=model2)
-        self.lr_scheduler1 = build_lr_scheduler(args=args.model1, optimizer=self.optimizer1)
-        self.lr_scheduler2 = build_lr_scheduler(args=args.model2, optimizer=self.optimizer2)
-        self.optimizer1._lr_dev = self.sc.view(S_LR1)
-        self.optimizer2._lr_dev = self.sc.view(S_LR2)
-        self._set_grad_scale(self.optimizer1, self.optimizer2)
-        self._own_gather(self.optimizer1, self.optimizer2)
+        super().__init__(args, dp, [model1, model2], ema_model)
         if hasattr(model1, "dense_projection_high"):
             # main.py:152 discards the first student's neck outputs: their parameters never get a gradient (torch's SGD then skips them: no
             # weight decay, no momentum), so the necks are not computed at all and the optimizer stops at the backbone
@@ -655,11 +568,10 @@ class HPFGStep(_StepBase):
         self._w = 0.0
 
     def host_scalars(self, cur_itrs):
-        a = self.args
-        w = a.consistency * linear_rampup(cur_itrs // 150, a.consistency_rampup)
+        w = self._cons_w(cur_itrs, rampup=linear_rampup)
         h = self.sc.host
         h[S_LR1], h[S_LR2] = self._lr(self.optimizer1), self._lr(self.optimizer2)
-        h[S_ALPHA] = ema_alpha(cur_itrs, a.ema_decay)
+        h[S_ALPHA] = ema_alpha(cur_itrs, self.args.ema_decay)
         h[S_COEF_A:S_COEF_A + 5] = torch.tensor([0.5, 0.5, 0.0, 7.0 * w, 0.0])                 # model1: sup + 7w * pseudo Dice
         h[S_COEF_B:S_COEF_B + 5] = torch.tensor([0.5, 0.5, 0.0, 0.0, 0.0 if cur_itrs < 1000 else w])   # model2: sup + w * MSE
         h[3] = w
@@ -678,64 +590,33 @@ class HPFGStep(_StepBase):
         nl = label_img.shape[0]
         mix_un = cutmix_blend(label_img1, img_unlabel, cutmix_mask)
         batch_mix = torch.cat([label_img, mix_un], 0)
-        split = self.overlap
-        if split:      # student 1 (fed the CutMix batch) is independent of student 2 and the teacher until the losses: a stream of its own,
-            # forward and -- through autograd, which runs a backward node on the stream of its forward -- backward (see CPSStep)
-            cur = torch.cuda.current_stream(self.dev)
-            if getattr(self, "side2", None) is None:
-                self.side2 = torch.cuda.Stream(device=self.dev)
-            self.side2.wait_stream(cur)
-            with torch.cuda.stream(self.side2):
-                o1, _, _ = self.model1(batch_mix)
-        else:
+        # student 1 (fed the CutMix batch) is independent of student 2 and the teacher until the losses: a stream of its own, forward and
+        # backward (see CPSStep)
+        with self._fork(self._side2()):
             o1, _, _ = self.model1(batch_mix)
         volume = cat_batch(label_img, img_unlabel)
-        volume_t = volume
-        ot, th1, th2 = self._teacher_forward(self.ema_model, volume_t)
+        ot, th1, th2 = self._teacher_forward(volume)
         o2, h1, h2 = self.model2(volume)
-        self._join_teacher(ot, th1, th2)
-        if split:
-            cur.wait_stream(self.side2)
-            o1.record_stream(cur)
-            batch_mix.record_stream(self.side2)
+        self._join(self.side, ot, th1, th2)
+        self._join(self.side2, o1)
+        batch_mix.record_stream(self.side2)
         pseudo = argmax_labels(ot[nl:], target_label1, cutmix_mask[:, 0])
         r1 = seg_loss(o1, target_label, nl, coef=self.sc.view(S_COEF_A, 8), pseudo=pseudo, dp=self.dp)
         r2 = seg_loss(o2, target_label, nl, coef=self.sc.view(S_COEF_B, 8), teacher_logits=ot, dp=self.dp)
         contrast = self.dense_loss(h1, th1) + self.dense_loss(h2, th2)
         loss = r1[0] + r2[0] + self.sc.view(3)[0] * contrast
-        self.optimizer1.zero_grad()
-        self.optimizer2.zero_grad()
-        loss.backward()
-        self._join_backward(getattr(self, "side2", None))
+        self._backward(loss, self.side2)
         return {"loss": loss.detach(), "parts1": r1.detach(), "parts2": r2.detach(), "contrast": contrast.detach(),
                 "logits1": o1.detach(), "logits2": o2.detach(), "t_logits": ot}
 
-    def exchange(self):
-        self._reduce_grads(self.model1, self.model2)
-
     def device_update(self):
-        self.optimizer1.step(push_lr=False)
-        self.optimizer2.step(push_lr=False)
+        super().device_update()
         a = self.sc.view(S_ALPHA)
         update_ema_variables_backbone(self.model1, self.model2, self.args.ema_decay, 0, alpha_dev=a)
         update_ema_variables(self.model2, self.ema_model, self.args.ema_decay, 0, alpha_dev=a)
 
-    def device_step(self, label_img, target_label, label_img1, target_label1, img_unlabel, cutmix_mask):
-        r = self.device_fwd_bwd(label_img, target_label, label_img1, target_label1, img_unlabel, cutmix_mask)
-        self.exchange()
-        self.device_update()
-        return r
-
-    def after(self):
-        self.lr_scheduler1.step()
-        self.lr_scheduler2.step()
-
     def step(self, label_img, target_label, label_img1, target_label1, img_unlabel, cutmix_mask, cur_itrs):
-        self.host_scalars(cur_itrs)
-        self.sc.push()
-        r = self.device_step(label_img, target_label, label_img1, target_label1, img_unlabel, cutmix_mask)
-        self.after()
-        return r
+        return self.eager_step((label_img, target_label, label_img1, target_label1, img_unlabel, cutmix_mask), cur_itrs)
 
 
 class S4CVNetStep(_StepBase):
@@ -745,25 +626,13 @@ class S4CVNetStep(_StepBase):
     Pure recomposition of the hot-path kernels (noise_add, argmax_labels, the fused loss with an unlabelled-only consistency target)."""
 
     def __init__(self, model1, model2, ema_model, args, dp=None):
-        super().__init__(next(model1.parameters()).device, dp)
-        self.model1, self.model2, self.ema_model, self.args = model1, model2, ema_model, args
-        for m in (model1, model2, ema_model):
-            self._attach(m)
-        self.optimizer1 = build_optimizer(args=args.model1, model=model1)
-        self.optimizer2 = build_optimizer(args=args.model2, model=model2)
-        self.lr_scheduler1 = build_lr_scheduler(args=args.model1, optimizer=self.optimizer1)
-        self.lr_scheduler2 = build_lr_scheduler(args=args.model2, optimizer=self.optimizer2)
-        self.optimizer1._lr_dev = self.sc.view(S_LR1)
-        self.optimizer2._lr_dev = self.sc.view(S_LR2)
-        self._set_grad_scale(self.optimizer1, self.optimizer2)
-        self._own_gather(self.optimizer1, self.optimizer2)
+        super().__init__(args, dp, [model1, model2], ema_model)
 
     def host_scalars(self, cur_itrs):
-        a = self.args
-        w = a.consistency * linear_rampup(cur_itrs // 150, a.consistency_rampup)
+        w = self._cons_w(cur_itrs, rampup=linear_rampup)
         h = self.sc.host
         h[S_LR1], h[S_LR2] = self._lr(self.optimizer1), self._lr(self.optimizer2)
-        h[S_ALPHA] = ema_alpha(cur_itrs, a.ema_decay)
+        h[S_ALPHA] = ema_alpha(cur_itrs, self.args.ema_decay)
         h[S_COEF_A:S_COEF_A + 5] = torch.tensor([0.5, 0.5, 0.0, 7.0 * w, 0.0 if cur_itrs < 1000 else w])      # both students (:141-150)
         return w
 
@@ -773,59 +642,29 @@ class S4CVNetStep(_StepBase):
     def device_fwd_bwd(self, label_img, target_label, unlabel_img, noise):
         nl = label_img.shape[0]
         x = cat_batch(label_img, unlabel_img)
-        ot = self._teacher_forward(self.ema_model, noise_add(unlabel_img, noise))
-        if self.overlap:      # the U-Net on a stream of its own, forward and backward (see CPSStep)
-            cur = torch.cuda.current_stream(self.dev)
-            if getattr(self, "side2", None) is None:
-                self.side2 = torch.cuda.Stream(device=self.dev)
-            self.side2.wait_stream(cur)
-            with torch.cuda.stream(self.side2):
-                o1 = self.model1(x)
-            o2 = self.model2(x)
-            cur.wait_stream(self.side2)
-            o1.record_stream(cur)
-        else:
+        ot = self._teacher_forward(noise_add(unlabel_img, noise))
+        with self._fork(self._side2()):      # the U-Net on a stream of its own, forward and backward (see CPSStep)
             o1 = self.model1(x)
-            o2 = self.model2(x)
-        self._join_teacher(ot)
+        o2 = self.model2(x)
+        self._join(self.side2, o1)
+        self._join(self.side, ot)
         p1 = argmax_labels(o1[nl:])
         p2 = argmax_labels(o2[nl:])
         coef = self.sc.view(S_COEF_A, 8)
         r1 = seg_loss(o1, target_label, nl, coef=coef, pseudo=p2, teacher_logits=ot, dp=self.dp)
         r2 = seg_loss(o2, target_label, nl, coef=coef, pseudo=p1, teacher_logits=ot, dp=self.dp)
         loss = r1[0] + r2[0]
-        self.optimizer1.zero_grad()
-        self.optimizer2.zero_grad()
-        loss.backward()
-        self._join_backward(getattr(self, "side2", None))
+        self._backward(loss, self.side2)
         return {"loss": loss.detach(), "parts1": r1.detach(), "parts2": r2.detach(), "logits1": o1.detach(), "logits2": o2.detach(), "t_logits": ot}
 
-    def exchange(self):
-        self._reduce_grads(self.model1, self.model2)
-
     def device_update(self):
-        self.optimizer1.step(push_lr=False)
-        self.optimizer2.step(push_lr=False)
+        super().device_update()
         update_ema_variables(self.model2, self.ema_model, self.args.ema_decay, 0, alpha_dev=self.sc.view(S_ALPHA))
-
-    def device_step(self, label_img, target_label, unlabel_img, noise):
-        r = self.device_fwd_bwd(label_img, target_label, unlabel_img, noise)
-        self.exchange()
-        self.device_update()
-        return r
-
-    def after(self):
-        self.lr_scheduler1.step()
-        self.lr_scheduler2.step()
 
     def step(self, label_img, target_label, unlabel_img, cur_itrs, noise=None):
         if noise is None:
             noise = self.draw_noise(unlabel_img)
-        self.host_scalars(cur_itrs)
-        self.sc.push()
-        r = self.device_step(label_img, target_label, unlabel_img, noise)
-        self.after()
-        return r
+        return self.eager_step((label_img, target_label, unlabel_img, noise), cur_itrs)
 
 
 class GraphNotCapturable(RuntimeError):
@@ -862,10 +701,7 @@ class GraphedStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for i in range(warmup):
-                self.s.host_scalars(i + 1)
-                self.s.sc.push()
-                self.s.device_step(*self.static)
-                self.s.after()
+                self.s.eager_step(self.static, i + 1)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         if before_capture is not None:
@@ -901,7 +737,7 @@ class GraphedStep:
             # the bucket chain ends one graph and begins the next in the middle of backward: only legal while no second stream is forked
             # there, i.e. for steps with one trainable network (two students back-propagate on two streams: one exchange after both)
             overlap = (bool(getattr(dp, "overlap", False))
-                       and sum(1 for m in self._models() if any(p.requires_grad for p in m.parameters())) == 1)
+                       and sum(1 for m in self.s.models if any(p.requires_grad for p in m.parameters())) == 1)
             if overlap:
                 # the boundary runs on autograd's device thread: ending a capture from another thread than the one that began it
                 # needs the relaxed mode (which also tolerates the RCCL watchdog's event queries)
@@ -928,7 +764,7 @@ class GraphedStep:
                         dp.bucket_hook = None
                         self.graphs[-1].capture_end()
                 torch.cuda.current_stream().wait_stream(cap)
-                for m in self._models():
+                for m in self.s.models:
                     m._buckets_launched = False
             else:
                 prev, dp.overlap = getattr(dp, "overlap", False), False      # one blocking exchange between the two graphs
@@ -943,11 +779,8 @@ class GraphedStep:
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
                 self.out = self.s.device_step(*self.static)
 
-    def _models(self):
-        return [getattr(self.s, n) for n in ("model", "model1", "model2", "ema_model") if hasattr(self.s, n)]
-
     def _freeze_seed_updates(self, capturing: bool):
-        for m in self._models():
+        for m in self.s.models:
             m._graph_seed_mode = capturing
             if capturing:
                 m._graph_fwds = 0
@@ -960,7 +793,7 @@ class GraphedStep:
                 dst.copy_(src, non_blocking=_async_ok(src))
         self.s.host_scalars(cur_itrs, **kw)
         self.s.sc.push()          # eager H2D copy of this step's scalars from a fresh ring slot, ordered in front of the replay
-        for m in self._models():
+        for m in self.s.models:
             m.bump_graph_seed()      # (the U-Nets advance their seed words inside the captured forward; the SegFormer branch does it here)
         if self.split:
             dp = self.s.dp
@@ -986,8 +819,7 @@ class CTCTStep(CPSStep):
     weights differ (Dice-only pseudo-supervision, weight w instead of 0.5*w*(CE + Dice))."""
 
     def host_scalars(self, cur_itrs, cons_w=None):
-        a = self.args
-        w = a.consistency * sigmoid_rampup(cur_itrs // 150, a.consistency_rampup) if cons_w is None else cons_w
+        w = self._cons_w(cur_itrs, cons_w)
         h = self.sc.host
         h[S_LR1], h[S_LR2] = self._lr(self.optimizer1), self._lr(self.optimizer2)
         h[S_COEF_A:S_COEF_A + 5] = torch.tensor([0.5, 0.5, 0.0, w, 0.0])
@@ -995,9 +827,10 @@ class CTCTStep(CPSStep):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# Driver loops with the reference's names / signatures: same iteration law (two labelled iterators restarted on StopIteration,
-# return once cur_itrs > total_itrs), evaluation every ``step_size`` iterations through hpfg_amd.val.test_acdc, and best-Dice
-# checkpoints in the reference's dict format {"model", "optimizer", "lr_scheduler", "cur_itrs", "best_dice"}.
+# Driver loops with the reference's names / signatures, each only its set-up around one shared loop (``_LoopRunner.drive``): same
+# iteration law (labelled iterators restarted on StopIteration, return once cur_itrs > total_itrs), evaluation every ``step_size``
+# iterations through hpfg_amd.val.test_acdc, and best-Dice checkpoints in the reference's dict format {"model", "optimizer",
+# "lr_scheduler", "cur_itrs", "best_dice"}.
 #
 # Every loop runs the path bench.py times: iteration 1 is an eager step (it allocates the engines' workspaces and IS iteration 1),
 # iteration 2 captures the step into ONE hipGraph on static input buffers, every later iteration is one copy per input (host -> the static
@@ -1071,16 +904,19 @@ def _async_ok(src: torch.Tensor) -> bool:
 
 
 class _LoopRunner:
-    """One training iteration of a driver loop: eager for iteration 1, captured at iteration 2, replayed afterwards (see the section header)."""
+    """The iteration law of every driver loop (``drive``), and one training iteration of it: eager for iteration 1, captured at iteration 2,
+    replayed afterwards (see the section header)."""
 
-    def __init__(self, st, args, slog: ScalarLog, vec_keys, host_fn):
-        self.st, self.args, self.slog, self.vec_keys, self.host_fn = st, args, slog, vec_keys, host_fn
+    def __init__(self, st, args, width: int, emit, vec_keys, host_fn):
+        """The iteration's scalars: the step's vectors ``vec_keys`` (``width`` floats together) and ``host_fn()``, named by ``emit`` (ScalarLog)."""
+        self.st, self.args, self.vec_keys, self.host_fn = st, args, vec_keys, host_fn
+        self.dev = torch.device(args.device)
+        self.slog = ScalarLog(self.dev, width, emit, getattr(args, "writer", None), int(getattr(args, "log_every", 50) or 50))
         self.graph_ok = bool(getattr(args, "hipgraph", True)) and os.environ.get("HPFG_LOOP_GRAPH", "1") == "1"
         self.runner, self.n = None, 0
-        self.dev = torch.device(args.device)
         dp = getattr(args, "dp", None)
-        if dp is not None and slog.check is None:          # a poll that expired means partial sums: noticed within `log_every` iterations
-            slog.check = dp.check_peer_errors
+        if dp is not None:          # a poll that expired means partial sums: noticed within `log_every` iterations
+            self.slog.check = dp.check_peer_errors
 
     def _to_dev(self, t):
         t = t.to(self.dev, non_blocking=_async_ok(t))
@@ -1104,20 +940,42 @@ class _LoopRunner:
             if self.runner is not None and all(tuple(a.shape) == tuple(b.shape) for a, b in zip(inputs, self.runner.static)):
                 r = self.runner.step(list(inputs), cur_itrs, **kw)          # copies (and converts) each input into its static buffer, replays
         if r is None:          # the eager form of the same iteration (what every step object's .step() does)
-            self.st.host_scalars(cur_itrs, **kw)
-            self.st.sc.push()
-            r = self.st.device_step(*[self._to_dev(t) for t in inputs])
-            self.st.after()
+            r = self.st.eager_step((self._to_dev(t) for t in inputs), cur_itrs, **kw)
         self.slog.add(cur_itrs, [r[k] for k in self.vec_keys], self.host_fn())
         return r
 
+    def drive(self, loader, inputs_of, test_loader, evals):
+        """One iteration per batch of `loader`, its step inputs made by ``inputs_of(batch)`` (which also draws the per-iteration random
+        inputs, in the reference's order); the peer check after each, and every ``step_size`` iterations the evaluations ``evals``, a list of
+        (_Best, network, optimizer, lr_scheduler, name); returns once cur_itrs > total_itrs (at most total_itrs // len(loader) + 1 epochs)
+        with the per-iteration total loss."""
+        args, cur_itrs = self.args, 0
+        for _ in range(args.total_itrs // len(loader) + 1):
+            for batch in loader:
+                cur_itrs += 1
+                self(inputs_of(batch), cur_itrs)
+                _check_peers(args, cur_itrs)
+                if test_loader is not None and cur_itrs % args.step_size == 0:
+                    for best, model, optimizer, lr_scheduler, name in evals:
+                        best(model, optimizer, lr_scheduler, test_loader, cur_itrs, name)
+                if cur_itrs > args.total_itrs:
+                    _check_peers(args, cur_itrs, final=True)
+                    return self.slog.losses()
+        _check_peers(args, cur_itrs, final=True)
+        return self.slog.losses()
 
-def _writer(args):
-    return getattr(args, "writer", None)
 
+def _with_labels(label_loader, extra=None):
+    """inputs_of for the drivers that iterate the unlabelled loader with the labelled one cycled beside it:
+    [label_img, target_label, unlabel_img] + extra(unlabel_img)."""
+    labels = _cycle(label_loader)
 
-def _log_every(args):
-    return int(getattr(args, "log_every", 50) or 50)
+    def inputs_of(batch):
+        unlabel_img, _ = batch
+        label_img, target_label = next(labels)
+        return [label_img, target_label, unlabel_img] + (list(extra(unlabel_img)) if extra is not None else [])
+
+    return inputs_of
 
 
 def _sup_of(row, o=0):
@@ -1154,10 +1012,6 @@ class _Best:
         return dice
 
 
-def _due(cur_itrs, args, test_loader):
-    return test_loader is not None and cur_itrs % args.step_size == 0
-
-
 def _check_peers(args, cur_itrs, final=False):
     """Data parallel with the peer exchanges: a kernel whose poll for a peer's value expired carried on with partial sums (it must not hang
     the GPU) and set a device word -- stop training on it at the evaluation cadence and at the end, not silently update weights from it."""
@@ -1171,22 +1025,9 @@ def Supervise(model, train_loader, test_loader, args):
     st = SupervisedStep(model, args, getattr(args, "dp", None))
     best = _Best(args, "model", path_fmt="model_{:.4f}.pth")
     model.train()
-    slog = ScalarLog(torch.device(args.device), 8, lambda row, h: {"supervise/loss": row[0], "supervise/lr": h["lr"]}, _writer(args), _log_every(args))
-    run = _LoopRunner(st, args, slog, ["parts"], lambda: {"lr": st._lr(st.optimizer)})
-    cur_itrs = 0
-    max_epoch = args.total_itrs // len(train_loader) + 1
-    for epoch in range(max_epoch):
-        for img, label_true in train_loader:
-            cur_itrs += 1
-            run([img, label_true], cur_itrs)
-            _check_peers(args, cur_itrs)
-            if _due(cur_itrs, args, test_loader):
-                best(model, st.optimizer, st.lr_scheduler, test_loader, cur_itrs)
-            if cur_itrs > args.total_itrs:
-                _check_peers(args, cur_itrs, final=True)
-                return slog.losses()
-    _check_peers(args, cur_itrs, final=True)
-    return slog.losses()
+    emit = lambda row, h: {"supervise/loss": row[0], "supervise/lr": h["lr"]}
+    run = _LoopRunner(st, args, 8, emit, ["parts"], lambda: {"lr": st._lr(st.optimizer)})
+    return run.drive(train_loader, list, test_loader, [(best, model, st.optimizer, st.lr_scheduler, "test")])      # batch = (img, label_true)
 
 
 def Mean_Teacher(model, ema_model, label_loader, unlabel_loader, test_loader, args):
@@ -1195,37 +1036,20 @@ def Mean_Teacher(model, ema_model, label_loader, unlabel_loader, test_loader, ar
     best, best_ema = _Best(args, "model", "model_save_path"), _Best(args, "ema", "ema_model_save_path")
     model.train()
     ema_model.train()          # the teacher stays in train mode (2017_03...py:70)
-    w = [0.0]
     emit = lambda row, h: {"mean_teacher/loss": row[0], "mean_teacher/lr": h["lr"], "mean_teacher/consistency_weight": h["w"]}
-    slog = ScalarLog(torch.device(args.device), 8, emit, _writer(args), _log_every(args))
-    run = _LoopRunner(st, args, slog, ["parts"], lambda: {"lr": st._lr(st.optimizer), "w": float(st.sc.host[S_COEF_A + 4])})
-    cur_itrs = 0
-    labels = _cycle(label_loader)
-    max_epoch = args.total_itrs // len(unlabel_loader) + 1
-    for epoch in range(max_epoch):
-        for unlabel_img, _ in unlabel_loader:
-            cur_itrs += 1
-            label_img, target_label = next(labels)
-            run([label_img, target_label, unlabel_img], cur_itrs)
-            _check_peers(args, cur_itrs)
-            if _due(cur_itrs, args, test_loader):
-                best(model, st.optimizer, st.lr_scheduler, test_loader, cur_itrs, "model")
-                best_ema(ema_model, st.optimizer, st.lr_scheduler, test_loader, cur_itrs, "ema")
-            if cur_itrs > args.total_itrs:
-                _check_peers(args, cur_itrs, final=True)
-                return slog.losses()
-    _check_peers(args, cur_itrs, final=True)
-    return slog.losses()
+    run = _LoopRunner(st, args, 8, emit, ["parts"], lambda: {"lr": st._lr(st.optimizer), "w": float(st.sc.host[S_COEF_A + 4])})
+    return run.drive(unlabel_loader, _with_labels(label_loader), test_loader,
+                     [(best, model, st.optimizer, st.lr_scheduler, "model"), (best_ema, ema_model, st.optimizer, st.lr_scheduler, "ema")])
 
 
-def _teacher_student_loop(st, tag, model, ema_model, label_loader, unlabel_loader, test_loader, args, extra_inputs, extra_scalars=None):
-    """The loop the teacher / student drivers besides Mean_Teacher share (2022_02_ISBI_ICT-MedSeg_ACDC.py:93-190,
-    2019_07_MICCAI_Uncertainty_Aware_ACDC.py:109-217): one unlabelled batch per iteration, the labelled loader cycled beside it, the
-    per-iteration random inputs drawn on the host side of the (captured) step in the reference's order, both networks evaluated every
-    ``step_size`` iterations.  Scalars: <tag>/loss, /lr, /consistency_weight, /consistency_loss [+ extra_scalars(st)]."""
+def _teacher_student(st, tag, label_loader, unlabel_loader, test_loader, args, extra_inputs, extra_scalars=None):
+    """The set-up the teacher / student drivers besides Mean_Teacher share (2022_02_ISBI_ICT-MedSeg_ACDC.py:93-190,
+    2019_07_MICCAI_Uncertainty_Aware_ACDC.py:109-217): the per-iteration random inputs ``extra_inputs(unlabel_img)`` drawn on the host side
+    of the (captured) step in the reference's order, both networks evaluated every ``step_size`` iterations.  Scalars: <tag>/loss, /lr,
+    /consistency_weight, /consistency_loss [+ extra_scalars(st)]."""
     best, best_ema = _Best(args, "model", "model_save_path"), _Best(args, "ema", "ema_model_save_path")
-    model.train()
-    ema_model.train()
+    st.model.train()
+    st.ema_model.train()
 
     def emit(row, h):
         d = {f"{tag}/loss": row[0], f"{tag}/lr": h["lr"], f"{tag}/consistency_weight": h["w"], f"{tag}/consistency_loss": row[5]}
@@ -1238,32 +1062,16 @@ def _teacher_student_loop(st, tag, model, ema_model, label_loader, unlabel_loade
             h.update(extra_scalars(st))
         return h
 
-    slog = ScalarLog(torch.device(args.device), 8, emit, _writer(args), _log_every(args))
-    run = _LoopRunner(st, args, slog, ["parts"], host)
-    cur_itrs = 0
-    labels = _cycle(label_loader)
-    max_epoch = args.total_itrs // len(unlabel_loader) + 1
-    for epoch in range(max_epoch):
-        for unlabel_img, _ in unlabel_loader:
-            cur_itrs += 1
-            label_img, target_label = next(labels)
-            run([label_img, target_label, unlabel_img] + list(extra_inputs(unlabel_img)), cur_itrs)
-            _check_peers(args, cur_itrs)
-            if _due(cur_itrs, args, test_loader):
-                best(model, st.optimizer, st.lr_scheduler, test_loader, cur_itrs, "test_model")
-                best_ema(ema_model, st.optimizer, st.lr_scheduler, test_loader, cur_itrs, "test_ema_model")
-            if cur_itrs > args.total_itrs:
-                _check_peers(args, cur_itrs, final=True)
-                return slog.losses()
-    _check_peers(args, cur_itrs, final=True)
-    return slog.losses()
+    run = _LoopRunner(st, args, 8, emit, ["parts"], host)
+    return run.drive(unlabel_loader, _with_labels(label_loader, extra_inputs), test_loader,
+                     [(best, st.model, st.optimizer, st.lr_scheduler, "test_model"),
+                      (best_ema, st.ema_model, st.optimizer, st.lr_scheduler, "test_ema_model")])
 
 
 def ICT_MedSeg(model, ema_model, label_loader, unlabel_loader, test_loader, args):
     """2022_02_ISBI_ICT-MedSeg_ACDC.py:65-190: the mix factors are numpy Beta draws per iteration (:112) -- an input of the step."""
     st = ICTStep(model, ema_model, args, getattr(args, "dp", None))
-    return _teacher_student_loop(st, "ICT_MedSeg", model, ema_model, label_loader, unlabel_loader, test_loader, args,
-                                 lambda u: [st.draw_mix_factors(u.shape[0])])
+    return _teacher_student(st, "ICT_MedSeg", label_loader, unlabel_loader, test_loader, args, lambda u: [st.draw_mix_factors(u.shape[0])])
 
 
 def Uncertainty_Aware(model, ema_model, label_loader, unlabel_loader, test_loader, args):
@@ -1275,8 +1083,8 @@ def Uncertainty_Aware(model, ema_model, label_loader, unlabel_loader, test_loade
         n0, rest = st.draw_noise(u.to(args.device).float())
         return [n0, torch.stack(rest)]
 
-    return _teacher_student_loop(st, "Uncertainty_Aware", model, ema_model, label_loader, unlabel_loader, test_loader, args, noise,
-                                 lambda s: {"threshold": float(s.sc.host[S_THRESH])})
+    return _teacher_student(st, "Uncertainty_Aware", label_loader, unlabel_loader, test_loader, args, noise,
+                            lambda s: {"threshold": float(s.sc.host[S_THRESH])})
 
 
 def CPS(model1, model2, label_loader, unlabel_loader, test_loader, args, step_cls=None):
@@ -1294,28 +1102,12 @@ def CPS(model1, model2, label_loader, unlabel_loader, test_loader, args, step_cl
         sup = _sup_of(row, 0) + _sup_of(row, 8)          # 2021_06...py:124-128
         return {"mynet/loss": loss, "mynet/lr": h["lr1"], "mynet/consistency_weight": h["w"], "mynet/loss_semi": loss - sup, "mynet/loss_sup": sup}
 
-    slog = ScalarLog(torch.device(args.device), 16, emit, _writer(args), _log_every(args))
     wpos = S_COEF_A + 3
-    run = _LoopRunner(st, args, slog, ["parts1", "parts2"],
+    run = _LoopRunner(st, args, 16, emit, ["parts1", "parts2"],
                       lambda: {"lr1": st._lr(st.optimizer1), "lr2": st._lr(st.optimizer2),
                                "w": float(st.sc.host[wpos]) * (1.0 if ctct else 2.0)})          # CPS parks 0.5 * w there (0.5 * w * (CE + Dice))
-    cur_itrs = 0
-    labels = _cycle(label_loader)
-    max_epoch = args.total_itrs // len(unlabel_loader) + 1
-    for epoch in range(max_epoch):
-        for unlabel_img, _ in unlabel_loader:
-            cur_itrs += 1
-            label_img, target_label = next(labels)
-            run([label_img, target_label, unlabel_img], cur_itrs)
-            _check_peers(args, cur_itrs)
-            if _due(cur_itrs, args, test_loader):
-                best1(model1, st.optimizer1, st.lr_scheduler1, test_loader, cur_itrs, "model1")
-                best2(model2, st.optimizer2, st.lr_scheduler2, test_loader, cur_itrs, "model2")
-            if cur_itrs > args.total_itrs:
-                _check_peers(args, cur_itrs, final=True)
-                return slog.losses()
-    _check_peers(args, cur_itrs, final=True)
-    return slog.losses()
+    return run.drive(unlabel_loader, _with_labels(label_loader), test_loader,
+                     [(best1, model1, st.optimizer1, st.lr_scheduler1, "model1"), (best2, model2, st.optimizer2, st.lr_scheduler2, "model2")])
 
 
 def CTCT(model1, model2, label_loader, unlabel_loader, test_loader, args):
@@ -1336,28 +1128,12 @@ def S4CVnet(model1, model2, ema_model, label_loader, unlabel_loader, test_loader
         return {"S4CVnet/loss": loss, "S4CVnet/loss_semi": loss - sup, "S4CVnet/loss_sup": sup, "S4CVnet/lr1": h["lr1"], "S4CVnet/lr2": h["lr2"],
                 "S4CVnet/consistency_weight_cps": h["w"], "S4CVnet/consistency_weight_mt": h["w"]}
 
-    slog = ScalarLog(torch.device(args.device), 16, emit, _writer(args), _log_every(args))
-    run = _LoopRunner(st, args, slog, ["parts1", "parts2"],
+    run = _LoopRunner(st, args, 16, emit, ["parts1", "parts2"],
                       lambda: {"lr1": st._lr(st.optimizer1), "lr2": st._lr(st.optimizer2), "w": float(st.sc.host[S_COEF_A + 3]) / 7.0})
-    cur_itrs = 0
-    labels = _cycle(label_loader)
-    max_epoch = args.total_itrs // len(unlabel_loader) + 1
-    for epoch in range(max_epoch):
-        for img_unlabel, _ in unlabel_loader:
-            cur_itrs += 1
-            img_labeled, target_label = next(labels)
-            noise = st.draw_noise(img_unlabel.to(args.device).float())      # an INPUT of the (captured) step: drawn here, in the reference's order (:109)
-            run([img_labeled, target_label, img_unlabel, noise], cur_itrs)
-            _check_peers(args, cur_itrs)
-            if _due(cur_itrs, args, test_loader):
-                best1(model1, st.optimizer1, st.lr_scheduler1, test_loader, cur_itrs, "model1")
-                best2(model2, st.optimizer2, st.lr_scheduler2, test_loader, cur_itrs, "model2")
-                best_ema(ema_model, st.optimizer2, st.lr_scheduler2, test_loader, cur_itrs, "ema")
-            if cur_itrs > args.total_itrs:
-                _check_peers(args, cur_itrs, final=True)
-                return slog.losses()
-    _check_peers(args, cur_itrs, final=True)
-    return slog.losses()
+    # the noise is an INPUT of the (captured) step: drawn in the reference's order (:109)
+    return run.drive(unlabel_loader, _with_labels(label_loader, lambda u: [st.draw_noise(u.to(args.device).float())]), test_loader,
+                     [(best1, model1, st.optimizer1, st.lr_scheduler1, "model1"), (best2, model2, st.optimizer2, st.lr_scheduler2, "model2"),
+                      (best_ema, ema_model, st.optimizer2, st.lr_scheduler2, "ema")])
 
 
 def HPFG(model1, model2, ema_model, label_loader, unlabel_loader, test_loader, args):
@@ -1374,28 +1150,19 @@ def HPFG(model1, model2, ema_model, label_loader, unlabel_loader, test_loader, a
         return {"HPFG/loss": loss, "HPFG/loss_semi": loss - sup, "HPFG/loss_sup": sup, "HPFG/lr1": h["lr1"], "HPFG/lr2": h["lr2"],
                 "HPFG/consistency_weight_cps": h["w"], "HPFG/consistency_weight_mt": h["w"]}
 
-    slog = ScalarLog(torch.device(args.device), 17, emit, _writer(args), _log_every(args))
-    run = _LoopRunner(st, args, slog, ["parts1", "parts2", "contrast"],
+    run = _LoopRunner(st, args, 17, emit, ["parts1", "parts2", "contrast"],
                       lambda: {"lr1": st._lr(st.optimizer1), "lr2": st._lr(st.optimizer2), "w": float(st._w)})
-    cur_itrs = 0
     it_a, it_b = _cycle(label_loader), _cycle(label_loader)      # two independent labelled iterators (main.py:119-120)
-    max_epoch = args.total_itrs // len(unlabel_loader) + 1
-    for epoch in range(max_epoch):
-        for img_unlabel, _ in unlabel_loader:
-            cur_itrs += 1
-            label_img, target_label = next(it_a)
-            label_img1, target_label1 = next(it_b)
-            nl, nu = label_img.shape[0], img_unlabel.shape[0]
-            rep = nu // nl
-            cm = st.make_cutmix_mask(nu, (args.train_crop_size[0], args.train_crop_size[1]), device=torch.device(args.device))
-            run([label_img, target_label, label_img1.repeat(rep, 1, 1, 1), target_label1.repeat(rep, 1, 1), img_unlabel, cm], cur_itrs)
-            _check_peers(args, cur_itrs)
-            if _due(cur_itrs, args, test_loader):
-                best1(model1, st.optimizer1, st.lr_scheduler1, test_loader, cur_itrs, "model1")
-                best2(model2, st.optimizer2, st.lr_scheduler2, test_loader, cur_itrs, "model2")
-                best_ema(ema_model, st.optimizer2, st.lr_scheduler2, test_loader, cur_itrs, "model1")      # main.py:259-272 saves optimizer2 with it
-            if cur_itrs > args.total_itrs:
-                _check_peers(args, cur_itrs, final=True)
-                return slog.losses()
-    _check_peers(args, cur_itrs, final=True)
-    return slog.losses()
+
+    def inputs_of(batch):
+        img_unlabel, _ = batch
+        label_img, target_label = next(it_a)
+        label_img1, target_label1 = next(it_b)
+        nl, nu = label_img.shape[0], img_unlabel.shape[0]
+        rep = nu // nl
+        cm = st.make_cutmix_mask(nu, (args.train_crop_size[0], args.train_crop_size[1]), device=torch.device(args.device))
+        return [label_img, target_label, label_img1.repeat(rep, 1, 1, 1), target_label1.repeat(rep, 1, 1), img_unlabel, cm]
+
+    return run.drive(unlabel_loader, inputs_of, test_loader,
+                     [(best1, model1, st.optimizer1, st.lr_scheduler1, "model1"), (best2, model2, st.optimizer2, st.lr_scheduler2, "model2"),
+                      (best_ema, ema_model, st.optimizer2, st.lr_scheduler2, "model1")])      # main.py:259-272 saves optimizer2 with the EMA model

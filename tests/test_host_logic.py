@@ -173,3 +173,35 @@ def test_eval_zoom_index_is_scipys_mapping():
         assert np.array_equal(got, zoom(a, (H / h, W / w), order=0))
     cm = np.array([[5, 1, 0], [2, 4, 0], [1, 1, 0]])
     assert V.dice_from_counts(cm, 1) == 2 * 4 / (6 + 6) and V.dice_from_counts(cm, 2) == 0.0
+
+
+def test_driver_loop_iteration_law_evaluation_cadence_and_label_cycling():
+    """The drivers' shared loop with a stub step: one iteration per unlabelled batch, the labelled loader cycled beside it, the evaluations
+    every step_size iterations, and the return once cur_itrs > total_itrs (the reference's law), over more than one epoch."""
+    from hpfg_amd.train import _LoopRunner, _with_labels
+
+    class _Step:
+        def __init__(self):
+            self.calls = []
+
+        def eager_step(self, inputs, cur_itrs, **kw):
+            inputs = list(inputs)
+            self.calls.append((cur_itrs, [float(t) for t in inputs]))
+            return {"parts": torch.tensor([float(cur_itrs), 0.0])}
+
+    args = AttrDict(device="cpu", total_itrs=7, step_size=3, hipgraph=False, log_every=4)
+    unlabel = [(torch.tensor(100.0 + i), None) for i in range(3)]
+    label = [(torch.tensor(float(i)), torch.tensor(10.0 + i)) for i in range(2)]
+    st, evals = _Step(), []
+    run = _LoopRunner(st, args, 2, lambda row, h: {"t/loss": row[0]}, ["parts"], lambda: {})
+
+    def best(model, opt, sched, test_loader, cur_itrs, name):
+        evals.append((cur_itrs, model, opt, sched, test_loader, name))
+
+    losses = run.drive(unlabel, _with_labels(label, lambda u: [u + 1]), "test", [(best, "m", "o", "s", "model"), (best, "e", "o", "s", "ema")])
+    assert [c for c, _ in st.calls] == list(range(1, 9))                      # 7 // 3 + 1 = 3 epochs available; stops at 8 > 7
+    assert [x for _, x in st.calls] == [[i % 2, 10 + i % 2, 100 + i % 3, 101 + i % 3] for i in range(8)]
+    assert evals == [(k, m, "o", "s", "test", n) for k in (3, 6) for m, n in (("m", "model"), ("e", "ema"))]
+    assert losses.tolist() == [float(k) for k in range(1, 9)]
+    run.drive(unlabel, _with_labels(label), None, [(best, "m", "o", "s", "model")])
+    assert len(evals) == 4                                                   # no test loader: no evaluation
