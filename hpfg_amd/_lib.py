@@ -18,7 +18,7 @@ ACT_NONE, ACT_PLAIN, ACT_STRIDED, ACT_BNACT, ACT_BNACT_POOL, ACT_UP2X, ACT_DZ, A
 OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP = 0, 1, 2, 3          # hpfg_set_option
 LOSS_NSUM = 32
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 132
+VERSION = 133
 MATH_F32, MATH_BF16X3 = 0, 1
 
 
@@ -202,6 +202,11 @@ PROTOTYPES = {
     "hpfg_attn_mfma_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "hpfg_attn_mfma_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "hpfg_attn_mfma_blocks": (_i, [_i]),
+    "hpfg_attn_mfma_fwd_hd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "hpfg_attn_mfma_bwd_hd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "hpfg_attn_mfma_scratch_floats": (_l, [_i, _i, _i, _i]),
+    "hpfg_attn_fwd_hd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "hpfg_attn_bwd_hd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "hpfg_gemm_f32": (_i, [_p, _l, _l, _p, _l, _l, _p, _l, _i, _i, _i, _p, _i, _i, _p]),
     "hpfg_gemm_f32_splitk": (_i, [_p, _l, _l, _p, _l, _l, _p, _l, _i, _i, _i, _p, _i, _i, _p, _p]),
     "hpfg_gemm_f32_splits": (_i, [_i, _i, _i]),

@@ -13,6 +13,8 @@ __device__ __forceinline__ void bin_range(int i, int L, int S, int& b0, int& b1)
 
 // x: NHWC [N,H,W,C] (pixel stride ps).  grid (S*S + 1, N): block b < S*S writes pool[n, b, :] (bin by = b / S, bx = b % S), block S*S
 // writes gap[n, :] (unet.py:141-142, :146).  Threads own one channel each in 256 / C pixel slots; slots are summed in a fixed order.
+// More than 256 channels (the 512-wide stage 4 of MiT-B1): grid z walks chunks of 256 channels, one pixel slot each -- the sum of a
+// channel is then a single thread's, in pixel order.
 __global__ __launch_bounds__(256) void neck_pool_fwd_kernel(const float* __restrict__ x, int ps, int H, int W, int C, int S, float* __restrict__ gap,
                                                             float* __restrict__ pool) {
   __shared__ float sh[256];
@@ -22,8 +24,9 @@ __global__ __launch_bounds__(256) void neck_pool_fwd_kernel(const float* __restr
     bin_range(b / S, H, S, y0, y1);
     bin_range(b % S, W, S, x0, x1);
   }
-  const int slots = 256 / C;            // C <= 256
-  const int c = tid % C, slot = tid / C;
+  const int c0 = blockIdx.z * 256, Cc = C - c0 < 256 ? C - c0 : 256;      // this workgroup's channels [c0, c0 + Cc)
+  const int slots = 256 / Cc;
+  const int c = c0 + tid % Cc, slot = tid / Cc;
   const int bw = x1 - x0, npix = (y1 - y0) * bw;
   float s = 0.f;
   if (slot < slots) {          // four independent loads in flight per thread (a bin of the 224 x 224 logits is 49 pixels per slot: latency, not bytes)
@@ -45,12 +48,12 @@ __global__ __launch_bounds__(256) void neck_pool_fwd_kernel(const float* __restr
   }
   sh[tid] = s;
   __syncthreads();
-  if (tid < C) {
+  if (tid < Cc) {
     float t = 0.f;
-    for (int k = 0; k < slots; ++k) t += sh[k * C + tid];
+    for (int k = 0; k < slots; ++k) t += sh[k * Cc + tid];
     t /= (float)npix;
-    if (b < S * S) pool[((long)n * S * S + b) * C + tid] = t;
-    else gap[(long)n * C + tid] = t;
+    if (b < S * S) pool[((long)n * S * S + b) * C + c0 + tid] = t;
+    else gap[(long)n * C + c0 + tid] = t;
   }
 }
 
@@ -173,10 +176,10 @@ __global__ __launch_bounds__(1024) void ntxent_rows_kernel(const float* __restri
 }  // namespace
 
 extern "C" int hpfg_neck_pool_fwd(const float* x, int pstride, int N, int H, int W, int C, int S, float* gap, float* pool, void* stream) {
-  HPFG_ARG_CHECK(x && gap && pool && N > 0 && H > 0 && W > 0 && C >= 1 && C <= 256 && S >= 1 && S <= H && S <= W && pstride >= C,
-                 "neck_pool_fwd: bad args (C=%d S=%d)", C, S);
+  HPFG_ARG_CHECK(x && gap && pool && N > 0 && H > 0 && W > 0 && C >= 1 && C <= 1024 && S >= 1 && S <= H && S <= W && pstride >= C,
+                 "neck_pool_fwd: bad args (C=%d: at most 1024 channels; S=%d: at most the map's %d x %d)", C, S, H, W);
   const bool tiles = H % S == 0 && W % S == 0;
-  hipLaunchKernelGGL(neck_pool_fwd_kernel, dim3(S * S + (tiles ? 0 : 1), N), dim3(256), 0, (hipStream_t)stream, x, pstride, H, W, C, S, gap, pool);
+  hipLaunchKernelGGL(neck_pool_fwd_kernel, dim3(S * S + (tiles ? 0 : 1), N, (C + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, pstride, H, W, C, S, gap, pool);
   if (tiles) hipLaunchKernelGGL(gap_from_pool_kernel, dim3((N * C + 127) / 128), dim3(128), 0, (hipStream_t)stream, pool, N, C, S * S, gap);
   return hpfg_launch_status("neck_pool_fwd_kernel");
 }

@@ -253,9 +253,10 @@ __global__ __launch_bounds__(256) void rows_sum_kernel(const float* __restrict__
   if (wave == 0 && o < n) out[o] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
 }
 
-// ---- attention core: thread per query, K / V of one (batch, head) in LDS; M <= 64 keys, head dim 32 ---------------------------------
-constexpr int AD = 32, AM = 64;
-// q [B,N,h,32] (row stride C = h*32), kv [B,M,2,h,32] (the kv Linear's output), out [B,N,h,32]
+// ---- attention core: thread per query, K / V of one (batch, head) in LDS; M <= 64 keys, head dim AD = 32 or 64 ---------------------------------
+constexpr int AM = 64;
+// q [B,N,h,AD] (row stride C = h*AD), kv [B,M,2,h,AD] (the kv Linear's output), out [B,N,h,AD]
+template <int AD>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ kv, float* __restrict__ out, int N, int M,
                                                        int heads, float scale) {
   __shared__ float ks[AM][AD], vs[AM][AD];
@@ -309,6 +310,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
 
 // backward per query: recompute P, then dq (in place of nothing else to reduce) and the two [B,h,N,M] matrices P and dS that the host
 // turns into dV = P^T dO and dK = scale * dS^T Q with library GEMMs.
+template <int AD>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__ q, const float* __restrict__ kv, const float* __restrict__ dout,
                                                        float* __restrict__ dq, float* __restrict__ P, float* __restrict__ dS, int N, int M, int heads,
                                                        float scale) {
@@ -906,17 +908,33 @@ extern "C" int hpfg_ln_bwd(const float* x, const float* dy, const float* gamma, 
   return hpfg_launch_status("ln_bwd_kernel");
 }
 
-extern "C" int hpfg_attn_fwd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, float scale, void* stream) {
-  HPFG_ARG_CHECK(q && kv && out && B > 0 && N > 0 && M > 0 && M <= AM && heads > 0, "attn_fwd: bad args (at most %d keys, head dim %d)", AM, AD);
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3((N + 255) / 256, heads, B), dim3(256), 0, (hipStream_t)stream, q, kv, out, N, M, heads, scale);
+extern "C" int hpfg_attn_fwd_hd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, int head_dim, float scale, void* stream) {
+  HPFG_ARG_CHECK(q && kv && out && B > 0 && N > 0 && M > 0 && M <= AM && heads > 0 && (head_dim == 32 || head_dim == 64),
+                 "attn_fwd: bad args (at most %d keys, head dim 32 or 64, got %d keys, head dim %d)", AM, M, head_dim);
+  const dim3 grid((N + 255) / 256, heads, B);
+  if (head_dim == 32) hipLaunchKernelGGL(attn_fwd_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, q, kv, out, N, M, heads, scale);
+  else hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, q, kv, out, N, M, heads, scale);
   return hpfg_launch_status("attn_fwd_kernel");
+}
+
+extern "C" int hpfg_attn_bwd_hd(const float* q, const float* kv, const float* dout, float* dq, float* P, float* dS, int B, int N, int M, int heads,
+                                int head_dim, float scale, void* stream) {
+  HPFG_ARG_CHECK(q && kv && dout && dq && P && dS && B > 0 && N > 0 && M > 0 && M <= AM && heads > 0 && (head_dim == 32 || head_dim == 64),
+                 "attn_bwd: bad args (at most %d keys, head dim 32 or 64, got %d keys, head dim %d)", AM, M, head_dim);
+  const dim3 grid((N + 255) / 256, heads, B);
+  if (head_dim == 32) hipLaunchKernelGGL(attn_bwd_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, q, kv, dout, dq, P, dS, N, M, heads, scale);
+  else hipLaunchKernelGGL(attn_bwd_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, q, kv, dout, dq, P, dS, N, M, heads, scale);
+  return hpfg_launch_status("attn_bwd_kernel");
+}
+
+/* head dim 32: the entry points older callers bind */
+extern "C" int hpfg_attn_fwd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, float scale, void* stream) {
+  return hpfg_attn_fwd_hd(q, kv, out, B, N, M, heads, 32, scale, stream);
 }
 
 extern "C" int hpfg_attn_bwd(const float* q, const float* kv, const float* dout, float* dq, float* P, float* dS, int B, int N, int M, int heads,
                              float scale, void* stream) {
-  HPFG_ARG_CHECK(q && kv && dout && dq && P && dS && B > 0 && N > 0 && M > 0 && M <= AM && heads > 0, "attn_bwd: bad args");
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3((N + 255) / 256, heads, B), dim3(256), 0, (hipStream_t)stream, q, kv, dout, dq, P, dS, N, M, heads, scale);
-  return hpfg_launch_status("attn_bwd_kernel");
+  return hpfg_attn_bwd_hd(q, kv, dout, dq, P, dS, B, N, M, heads, 32, scale, stream);
 }
 
 extern "C" int hpfg_dwgelu_fwd(const float* x, const float* w9, const float* bias, float* y, int B, int H, int W, int C, void* stream) {

@@ -1,4 +1,5 @@
-"""SegFormer-B0 for the CTCT cross-teaching branch.
+"""SegFormer-B0 for the CTCT cross-teaching branch and SegFormer_Plus (MiT-B1 + the two projection necks of
+UNet_Plus: the second backbone the reference ships its own HPFG method for, model/segformer.py:414-432).
 
 Same module tree, parameter names and constructor order as the reference's ``model/segformer.py`` (MiT :213-272, SegFormerHead
 :298-320, SegFormer :397-411), so ``state_dict()`` interchanges and a seed gives the same initial weights.  Where the work runs:
@@ -9,7 +10,7 @@ Same module tree, parameter names and constructor order as the reference's ``mod
     stride, so it is a GEMM over non-overlapping patches), the patch embeddings (after a HIP im2col), the head's per-stage projections and
     its 1x1 fuse / prediction convs.  No rocBLAS / hipBLASLt call is left (HPFG_MATH=f32 switches them to the exact-fp32 MFMA GEMM);
   - the attention core softmax(q k^T / sqrt(d)) v on the matrix cores (``csrc/attn.hip``: at most 64 keys after the spatial reduction,
-    head dim 32 = one MFMA k-step; forward, dQ and dK / dV kernels without LDS transposes of the probabilities);
+    head dim 32 = one MFMA k-step (B0) or 64 = two (B1); forward, dQ and dK / dV kernels without LDS transposes of the probabilities);
   - every LayerNorm, depthwise 3x3 + GELU of the Mix-FFN, the head's bilinear resizes and its BatchNorm(train) + ReLU + Dropout2d,
     im2col / col2im of the overlap patch embeddings, residual adds with their drop-path factor (``csrc/tokens.hip``);
 * the head never builds the 4E-channel concat: ``linear_fuse`` (bias-free 1x1 conv) is applied per stage at the stage's resolution and the four
@@ -29,9 +30,10 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from .. import heads
 from ..ops_tokens import attention, bn_relu_dropout, dwconv_gelu, im2col, layer_norm, linear, residual_scale, resize_bilinear, resize_sum
 
-MIT_SETTINGS = {"B0": [[32, 64, 160, 256], [2, 2, 2, 2]]}
+MIT_SETTINGS = {"B0": [[32, 64, 160, 256], [2, 2, 2, 2]], "B1": [[64, 128, 320, 512], [2, 2, 2, 2]]}
 HEADS, SR = [1, 2, 5, 8], [8, 4, 2, 1]
 
 
@@ -124,7 +126,7 @@ class MiT(nn.Module):
     def __init__(self, model_name: str = "B0", in_channels: int = 3):
         super().__init__()
         if model_name not in MIT_SETTINGS:
-            raise NotImplementedError(f"MiT-{model_name}: only B0 (the CTCT configuration) is built")
+            raise NotImplementedError(f"MiT-{model_name}: only {sorted(MIT_SETTINGS)} are built (B0: the CTCT configuration, B1: SegFormer_Plus)")
         embed_dims, depths = MIT_SETTINGS[model_name]
         self.embed_dims, self.depths = embed_dims, depths
         self.patch_embed1 = PatchEmbed(in_channels, embed_dims[0], 7, 4)
@@ -253,3 +255,56 @@ class SegFormer(nn.Module):
     def bump_graph_seed(self):
         """GraphedStep hook (the U-Net engines advance their dropout seed word here): nothing to do -- drop-path and Dropout2d draw from
         the torch device generator, whose state a captured graph advances by itself at every replay."""
+
+
+NECK_POOL = 4          # projection_conv's AdaptiveAvgPool2d((4, 4)) (model/segformer.py:364,379)
+
+
+class SegFormer_Plus(nn.Module):
+    """MiT-B1 + SegFormerHead + the two ``projection_conv`` necks (reference model/segformer.py:414-432; same construction order and
+    ``state_dict`` keys).  ``forward`` returns ``(logits, high, head)``, each neck output a ``(global [N,128], dense [N,128,16])`` pair:
+    ``high`` on the stage-4 tokens [B, H/32 * W/32, 512] -- which already are the NHWC feature map ``heads.projection_neck`` prefers --
+    and ``head`` on the logits.  ``skip_necks`` (set by a step that discards them, HPFG's first student) leaves them uncomputed."""
+
+    def __init__(self, image_size=(224, 224), in_channels=3, num_classes=4, model_name: str = "B1"):
+        super().__init__()
+        from .unet import _neck
+        side = [int(s) // 32 for s in image_size]
+        if min(side) < NECK_POOL:
+            raise ValueError(f"SegFormer_Plus: image size {list(image_size)} gives a {side[0]} x {side[1]} stage-4 map, smaller than the necks' "
+                             f"{NECK_POOL} x {NECK_POOL} adaptive pooling; image sides must be at least {32 * NECK_POOL}")
+        self.encoder = MiT(model_name=model_name, in_channels=in_channels)
+        self.decoder = SegFormerHead(self.encoder.embed_dims, image_size=image_size, embed_dim=256, num_classes=num_classes)
+        self.dense_projection_high = _neck(self.encoder.embed_dims[-1], 2048)
+        self.dense_projection_head = _neck(num_classes, 1024)
+        self.external_draws = None        # (drop_path_draws, dropout_mask): replay given random draws (tests)
+        self.skip_necks = False
+
+    def backbone_numel(self) -> int:
+        """encoder + decoder parameters: the leading part of ``parameters()`` (and of the flat buffers an optimizer lays them into)."""
+        return sum(p.numel() for m in (self.encoder, self.decoder) for p in m.parameters())
+
+    def _backbone(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("hpfg_amd.SegFormer_Plus runs on the GPU only: its LayerNorm / attention / DWConv kernels have no CPU fallback")
+        if x.shape[-2] // 32 < NECK_POOL or x.shape[-1] // 32 < NECK_POOL:
+            raise ValueError(f"SegFormer_Plus: a {x.shape[-2]} x {x.shape[-1]} input gives a stage-4 map smaller than the necks' {NECK_POOL} x "
+                             f"{NECK_POOL} adaptive pooling; image sides must be at least {32 * NECK_POOL}")
+        dp, mask = self.external_draws if self.external_draws is not None else (None, None)
+        feats = self.encoder(x.float(), dp)
+        return self.decoder(feats, mask), feats[-1]
+
+    def val(self, x):
+        return self._backbone(x)[0]
+
+    def forward(self, x):
+        logits, (t4, H4, W4) = self._backbone(x)
+        if self.skip_necks:
+            return logits, None, None
+        B = t4.shape[0]
+        high = heads.projection_neck(self.dense_projection_high, t4.view(B, H4, W4, -1).permute(0, 3, 1, 2), NECK_POOL)
+        head = heads.projection_neck(self.dense_projection_head, logits, NECK_POOL)
+        return logits, high, head
+
+    def bump_graph_seed(self):
+        """GraphedStep hook: nothing to do (see SegFormer.bump_graph_seed)."""

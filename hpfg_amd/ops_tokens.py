@@ -64,6 +64,9 @@ def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torc
     return _LayerNorm.apply(x, gamma, beta)
 
 
+HEAD_DIMS, MAX_KEYS = (32, 64), 64          # what csrc/attn.hip and the exact-fp32 kernels of csrc/tokens.hip are built for
+
+
 class _Attention(torch.autograd.Function):
     """softmax(scale q k^T) v on the matrix cores (csrc/attn.hip): split-bf16 MFMA products in the default math mode; HPFG_MATH=f32 keeps
     the exact-fp32 one-thread-per-query kernels of csrc/tokens.hip (dK / dV then through the exact GEMM)."""
@@ -77,10 +80,11 @@ class _Attention(torch.autograd.Function):
         M = kvc.shape[1]
         out = torch.empty_like(qc)
         ctx.math = gemm_math()
+        d = C_ // heads
         if ctx.math == "bf16x3":
-            L.check(lib.hpfg_attn_mfma_fwd(L.ptr(qc), L.ptr(kvc), L.ptr(out), B, N, M, heads, scale, _st(q)), "attn_mfma_fwd")
+            L.check(lib.hpfg_attn_mfma_fwd_hd(L.ptr(qc), L.ptr(kvc), L.ptr(out), B, N, M, heads, d, scale, _st(q)), "attn_mfma_fwd")
         else:
-            L.check(lib.hpfg_attn_fwd(L.ptr(qc), L.ptr(kvc), L.ptr(out), B, N, M, heads, scale, _st(q)), "attn_fwd")
+            L.check(lib.hpfg_attn_fwd_hd(L.ptr(qc), L.ptr(kvc), L.ptr(out), B, N, M, heads, d, scale, _st(q)), "attn_fwd")
         ctx.save_for_backward(qc, kvc)
         ctx.heads, ctx.scale = heads, scale
         return out
@@ -96,13 +100,13 @@ class _Attention(torch.autograd.Function):
         dq = torch.empty_like(q)
         if ctx.math == "bf16x3":
             dkv = torch.empty_like(kv)
-            scratch = torch.empty(B * h * lib.hpfg_attn_mfma_blocks(N) * 2 * 64 * 32, dtype=torch.float32, device=q.device)
-            L.check(lib.hpfg_attn_mfma_bwd(L.ptr(q), L.ptr(kv), L.ptr(do), L.ptr(dq), L.ptr(dkv), L.ptr(scratch), B, N, M, h, ctx.scale, _st(q)),
+            scratch = torch.empty(lib.hpfg_attn_mfma_scratch_floats(B, N, h, d), dtype=torch.float32, device=q.device)
+            L.check(lib.hpfg_attn_mfma_bwd_hd(L.ptr(q), L.ptr(kv), L.ptr(do), L.ptr(dq), L.ptr(dkv), L.ptr(scratch), B, N, M, h, d, ctx.scale, _st(q)),
                     "attn_mfma_bwd")
             return dq, dkv, None, None
         P = torch.empty(B, h, N, M, dtype=torch.float32, device=q.device)
         dS = torch.empty_like(P)
-        L.check(lib.hpfg_attn_bwd(L.ptr(q), L.ptr(kv), L.ptr(do), L.ptr(dq), L.ptr(P), L.ptr(dS), B, N, M, h, ctx.scale, _st(q)), "attn_bwd")
+        L.check(lib.hpfg_attn_bwd_hd(L.ptr(q), L.ptr(kv), L.ptr(do), L.ptr(dq), L.ptr(P), L.ptr(dS), B, N, M, h, d, ctx.scale, _st(q)), "attn_bwd")
         # dV = P^T dO, dK = scale * dS^T Q per (image, head): exact-fp32 MFMA GEMMs (hpfg_gemm_f32) writing straight into the [B,M,2,h,d] layout
         dkv = torch.empty(B, M, 2, h, d, dtype=torch.float32, device=q.device)
         st = _st(q)
@@ -119,8 +123,13 @@ class _Attention(torch.autograd.Function):
 
 
 def attention(q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
-    """softmax(scale * q k^T) v per head.  q [B,N,C], kv [B,M,2C] laid out [.., 2, heads, C/heads] (the kv Linear's output); C/heads == 32."""
-    assert q.shape[-1] // heads == 32 and kv.shape[-1] == 2 * q.shape[-1] and kv.shape[1] <= 64
+    """softmax(scale * q k^T) v per head.  q [B,N,C], kv [B,M,2C] laid out [.., 2, heads, C/heads] (the kv Linear's output); the head
+    dim C/heads is 32 (MiT-B0) or 64 (MiT-B1 and wider), at most 64 keys."""
+    C_ = q.shape[-1]
+    if C_ % heads or C_ // heads not in HEAD_DIMS:
+        raise ValueError(f"attention: head dim {C_}/{heads} is not built; the HIP attention kernels exist for head dims {HEAD_DIMS}")
+    if kv.shape[-1] != 2 * C_ or kv.shape[1] > MAX_KEYS:
+        raise ValueError(f"attention: kv {tuple(kv.shape)} must be [B, M <= {MAX_KEYS}, {2 * C_}] for q {tuple(q.shape)}")
     return _Attention.apply(q, kv, heads, scale)
 
 

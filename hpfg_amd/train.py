@@ -140,7 +140,7 @@ class _StepBase:
 
     def _build_optimizers(self):
         two = len(self.trainable) == 2
-        names, sub = (("1", "2"), (self.args.model1, self.args.model2)) if two else (("",), (self.args,))
+        names, sub = (("1", "2"), self._student_args()) if two else (("",), (self.args,))
         self.optimizers = [build_optimizer(args=a, model=m) for a, m in zip(sub, self.trainable)]
         self.lr_schedulers = [build_lr_scheduler(args=a, optimizer=o) for a, o in zip(sub, self.optimizers)]
         for n, m, o, s, lr_slot in zip(names, self.trainable, self.optimizers, self.lr_schedulers, (S_LR1, S_LR2)):
@@ -150,6 +150,10 @@ class _StepBase:
             o._lr_dev = self.sc.view(lr_slot)
         self._set_grad_scale(*self.optimizers)
         self._own_gather(*self.optimizers)
+
+    def _student_args(self):
+        """The optimizer recipes of a two-student step: the config's ``model1`` / ``model2`` sub-trees (an AttributeError without them)."""
+        return self.args.model1, self.args.model2
 
     def eager_step(self, inputs, cur_itrs, **kw):
         """One iteration, launched eagerly; ``kw`` goes to host_scalars.  (``inputs`` is unpacked after the push: a generator of device
@@ -213,9 +217,10 @@ class _StepBase:
                     if torch.is_tensor(u):
                         u.record_stream(cur)
 
-    def _teacher_forward(self, x):
-        """ema_model(x) under no_grad on the side stream; the caller joins it with ``_join(self.side, outputs)``."""
-        with self._fork(self.side), torch.no_grad():
+    def _teacher_forward(self, x, forked: bool = False):
+        """ema_model(x) under no_grad on the side stream; the caller joins it with ``_join(self.side, outputs)``.
+        forked: the side stream already waits for the current one at an earlier point (HPFGStep: before the second student was queued)."""
+        with (torch.cuda.stream(self.side) if forked else self._fork(self.side)), torch.no_grad():
             self._mark(2)
             out = self.ema_model(x)
             self._mark(3)
@@ -553,14 +558,27 @@ class CPSStep(_StepBase):
 
 class HPFGStep(_StepBase):
     def __init__(self, model1, model2, ema_model, args, dp=None):
+        from .model.segformer import SegFormer_Plus
         from .utils import Dense_Loss
+        from .utils.optim import FusedAdamW, flatten_parameters
+        plus = [isinstance(m, SegFormer_Plus) for m in (model1, model2, ema_model)]
+        if any(plus):
+            if not all(plus):
+                raise NotImplementedError("HPFGStep: mixed U-Net / SegFormer_Plus networks are not built (the three networks must be of one kind)")
+            if dp is not None:
+                raise NotImplementedError("HPFGStep: data parallel (dp is not None) with SegFormer_Plus networks is not built")
+            for m in (model1, model2, ema_model):      # one flat parameter buffer each: the optimizer steps and both EMA updates are single kernels
+                flatten_parameters(m)
+        # SegFormer_Plus draws drop-path factors and the Dropout2d mask from the torch device generator, which hands out its sequence in HOST
+        # call order whatever stream the kernels run on: the forwards are then issued as main.py:152-160 calls them -- model1, model2, teacher
+        self.reference_call_order = all(plus)
         super().__init__(args, dp, [model1, model2], ema_model)
         if hasattr(model1, "dense_projection_high"):
-            # main.py:152 discards the first student's neck outputs: their parameters never get a gradient (torch's SGD then skips them: no
-            # weight decay, no momentum), so the necks are not computed at all and the optimizer stops at the backbone
+            # main.py:152 discards the first student's neck outputs: their parameters never get a gradient (torch's SGD and AdamW then skip
+            # them: no weight decay, no momentum / moments), so the necks are not computed at all and the optimizer stops at the backbone
             model1.skip_necks = True
-            if isinstance(self.optimizer1, FusedSGD):
-                self.optimizer1.active_numel = model1._backbone_numel
+            if isinstance(self.optimizer1, (FusedSGD, FusedAdamW)):
+                self.optimizer1.active_numel = model1.backbone_numel()
         self.dense_loss = Dense_Loss(args.batch_size + args.unlabel_batch_size, self.dev)
         self.dense_loss.dp = dp      # global-batch mode: NT-Xent over the gathered features of all ranks (main.py:172 contrasts the whole batch)
         self.mask_generator = BoxMaskGenerator(prop_range=(0.25, 0.5), n_boxes=4, random_aspect_ratio=True, prop_by_area=True,
@@ -577,6 +595,11 @@ class HPFGStep(_StepBase):
         h[3] = w
         self._w = w
         return w
+
+    def _student_args(self):
+        """A flat config without model1 / model2 sub-trees -- the reference's own layout for this method -- gives both students the one
+        top-level recipe."""
+        return getattr(self.args, "model1", self.args), getattr(self.args, "model2", self.args)
 
     def make_cutmix_mask(self, n, shape, rng=None, device=None):
         """Host numpy masks (reference behaviour) or, with ``device``, the same masks rasterised on the GPU."""
@@ -595,8 +618,13 @@ class HPFGStep(_StepBase):
         with self._fork(self._side2()):
             o1, _, _ = self.model1(batch_mix)
         volume = cat_batch(label_img, img_unlabel)
-        ot, th1, th2 = self._teacher_forward(volume)
-        o2, h1, h2 = self.model2(volume)
+        if self.reference_call_order:
+            self.side.wait_stream(torch.cuda.current_stream(self.dev))      # the teacher's stream forks HERE: it does not wait for student 2's kernels
+            o2, h1, h2 = self.model2(volume)
+            ot, th1, th2 = self._teacher_forward(volume, forked=True)
+        else:
+            ot, th1, th2 = self._teacher_forward(volume)
+            o2, h1, h2 = self.model2(volume)
         self._join(self.side, ot, th1, th2)
         self._join(self.side2, o1)
         batch_mix.record_stream(self.side2)

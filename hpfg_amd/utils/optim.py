@@ -28,6 +28,10 @@ class FusedSGD(torch.optim.Optimizer):
         self.active_numel = None
 
     def zero_grad(self, set_to_none: bool = False):
+        if hasattr(self.model, "_hpfg_generic_flat"):      # a module laid out by flatten_parameters (SegFormer_Plus): see FusedAdamW.zero_grad
+            for p in self.model.parameters():
+                p.grad = None
+            return
         self.model.zero_flat_grad()          # one memset; p.grad views stay attached
         self.model.attach_grad_views()
 
@@ -41,6 +45,8 @@ class FusedSGD(torch.optim.Optimizer):
         """ema: optional (teacher_flat, numel, alpha_dev) -- the EMA teacher update of the same iteration rides along in the same launch
         (hpfg_sgd_ema_step; bit-identical to step() followed by utils.update_ema_variables)."""
         g = self.param_groups[0]
+        if hasattr(self.model, "_hpfg_generic_flat"):
+            gather_flat_grads(self.model, self.active_numel)
         flat, grad = self.model.flat_params, self.model.flat_grads
         if self._mom.data_ptr() == 0 or self._mom.numel() != flat.numel() or self._mom.device != flat.device:
             self._mom = torch.zeros_like(flat)
@@ -93,6 +99,23 @@ def flatten_parameters(model):
     model._hpfg_generic_flat = True      # gradients reach flat_grads only through FusedAdamW.gather_flat_grads()
 
 
+@torch.no_grad()
+def gather_flat_grads(model, active_numel=None):
+    """Pack the per-parameter gradients autograd left on a ``flatten_parameters`` module into ``model.flat_grads`` with ONE concat (a
+    parameter without a gradient contributes zeros).  active_numel: only the leading parameters that make up that many elements -- the
+    rest of the buffer is neither written here nor read by the optimizer kernels."""
+    ps, k = [], 0
+    for p in model.parameters():
+        if active_numel is not None and k >= active_numel:
+            break
+        ps.append(p)
+        k += p.numel()
+    assert active_numel is None or k == active_numel, "active_numel must end on a parameter boundary"
+    out = model.flat_grads if active_numel is None else model.flat_grads[:k]
+    torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in ps], out=out)
+    return model.flat_grads
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW(lr, weight_decay) -- betas (0.9, 0.999), eps 1e-8 as the reference leaves them (utils/__init__.py:17-19) -- as ONE
     HIP kernel over the model's flat parameter / gradient / moment buffers; learning rate and step count live on the device, so the
@@ -114,6 +137,9 @@ class FusedAdamW(torch.optim.Optimizer):
         # (data parallel: _StepBase._own_gather): the gradient exchange gathers, reduces in place, and step() consumes flat_grads as they
         # are; False (one rank): step() gathers.
         self.external_gather = False
+        # torch.optim.AdamW skips a parameter whose .grad is None: no moment update, no step, and no weight decay either.  A step that never
+        # back-propagates into a trailing part of the flat buffer (HPFG's first student: its necks) says so here, as on FusedSGD.
+        self.active_numel = None
         model._hpfg_flat_optimizer = self
 
     def zero_grad(self, set_to_none: bool = True):
@@ -122,11 +148,8 @@ class FusedAdamW(torch.optim.Optimizer):
         for p in self.model.parameters():
             p.grad = None
 
-    @torch.no_grad()
     def gather_flat_grads(self):
-        ps = [p for p in self.model.parameters()]
-        torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in ps], out=self.model.flat_grads)
-        return self.model.flat_grads
+        return gather_flat_grads(self.model, self.active_numel)
 
     def push_lr(self):
         self._lr_host[0] = float(self.param_groups[0]["lr"])
@@ -140,7 +163,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if push_lr:
             self.push_lr()
         st = torch.cuda.current_stream(flat.device).cuda_stream
-        L.check(L.load().hpfg_adamw_step(L.ptr(flat), L.ptr(grad), L.ptr(self._m), L.ptr(self._v), flat.numel(), L.ptr(self._lr_dev), L.ptr(self._step_dev),
+        n = flat.numel() if self.active_numel is None else int(self.active_numel)
+        L.check(L.load().hpfg_adamw_step(L.ptr(flat), L.ptr(grad), L.ptr(self._m), L.ptr(self._v), n, L.ptr(self._lr_dev), L.ptr(self._step_dev),
                                          float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale), st),
                 "adamw_step")
 

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 132
+#define HPFG_VERSION 133
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -424,6 +424,10 @@ int hpfg_attn_fwd(const float* q, const float* kv, float* out, int B, int N, int
 /* backward: dq, and the matrices P, dS [B,heads,N,M] from which dV = P^T dO and dK = scale * dS^T Q follow (GEMMs) */
 int hpfg_attn_bwd(const float* q, const float* kv, const float* dout, float* dq, float* P, float* dS, int B, int N, int M, int heads, float scale,
                   void* stream);
+/* the same two with the head dim as an argument (32 or 64: q [B,N,heads,head_dim], kv [B,M,2,heads,head_dim]); the two above are head_dim = 32 */
+int hpfg_attn_fwd_hd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, int head_dim, float scale, void* stream);
+int hpfg_attn_bwd_hd(const float* q, const float* kv, const float* dout, float* dq, float* P, float* dS, int B, int N, int M, int heads, int head_dim,
+                     float scale, void* stream);
 /* DWConv (3x3 depthwise, pad 1, :139-146) + F.gelu (:156) on [B,H,W,C]; w9 = the [C,1,3,3] weight transposed to [9][C] */
 int hpfg_dwgelu_fwd(const float* x, const float* w9, const float* bias, float* y, int B, int H, int W, int C, void* stream);
 int hpfg_dwgelu_bwd(const float* x, const float* w9, const float* bias, const float* dy, float* du /* scratch [B,H,W,C] */, float* dx, float* dw9,
@@ -485,6 +489,13 @@ int hpfg_attn_mfma_fwd(const float* q, const float* kv, float* out, int B, int N
 int hpfg_attn_mfma_bwd(const float* q, const float* kv, const float* dout, float* dq, float* dkv, float* scratch, int B, int N, int M, int heads,
                        float scale, void* stream);
 int hpfg_attn_mfma_blocks(int N);
+/* the same kernels with the head dim as an argument: 32 (bit-identical to the entry points above, which forward here) or 64 (MiT-B1: two
+ * MFMA k-steps per score tile, four d-tiles per output).  The backward's scratch holds hpfg_attn_mfma_scratch_floats(B, N, heads, head_dim)
+ * floats (= B * heads * hpfg_attn_mfma_blocks(N) * 2 * 64 * head_dim; -1 for a head dim that is not built). */
+int hpfg_attn_mfma_fwd_hd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, int head_dim, float scale, void* stream);
+int hpfg_attn_mfma_bwd_hd(const float* q, const float* kv, const float* dout, float* dq, float* dkv, float* scratch, int B, int N, int M, int heads,
+                          int head_dim, float scale, void* stream);
+long hpfg_attn_mfma_scratch_floats(int B, int N, int heads, int head_dim);
 
 /* ---- projection necks + Dense_Loss (UNet_Plus; reference model/unet.py:120-152, utils/loss/dense_loss.py:17-40) ------------------------ */
 /* C[m,n] = act(sum_k A(m,k) B(k,n) + bias[n]) in exact fp32 on the matrix cores; A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn], C row-major
@@ -519,7 +530,7 @@ int hpfg_col_sum(const float* x, long R, int M, long ldx, float* out /* [M] = su
 int hpfg_col_sum2(const float* x, long R, int M, long ldx, float* out, float* scratch /* hpfg_col_sum_splits(R) * M floats */, void* stream);
 int hpfg_col_sum_splits(long R);
 int hpfg_relu_bwd(float* dy, const float* y, long n, void* stream);                                         /* dy *= (y > 0): nn.ReLU backward */
-/* nn.AdaptiveAvgPool2d((1,1)) and ((S,S)) of an NHWC tensor in one launch (unet.py:141-142,146): gap [N,C], pool [N,S*S,C] */
+/* nn.AdaptiveAvgPool2d((1,1)) and ((S,S)) of an NHWC tensor in one launch (unet.py:141-142,146): gap [N,C], pool [N,S*S,C]; C <= 1024, S <= H, W */
 int hpfg_neck_pool_fwd(const float* x, int pstride, int N, int H, int W, int C, int S, float* gap, float* pool, void* stream);
 int hpfg_neck_pool_bwd(const float* dgap /* or NULL */, const float* dpool /* or NULL */, int N, int H, int W, int C, int S,
                        float* dx /* NHWC contiguous, overwritten */, void* stream);
