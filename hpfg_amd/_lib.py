@@ -16,9 +16,10 @@ LIB_PATH = os.path.join(_HERE, "lib", "libhpfg_hip.so")
 BN_MEAN, BN_RSTD, BN_SCALE, BN_SHIFT, BN_K1, BN_K2, BN_K3, BN_SPARE, BN_ROWS = range(9)
 ACT_NONE, ACT_PLAIN, ACT_STRIDED, ACT_BNACT, ACT_BNACT_POOL, ACT_UP2X, ACT_DZ, ACT_SPLIT16, ACT_UPBWD = range(9)
 OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP = 0, 1, 2, 3          # hpfg_set_option
-LOSS_NSUM = 32
+LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
+LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 133
+VERSION = 134
 MATH_F32, MATH_BF16X3 = 0, 1
 
 
@@ -190,6 +191,7 @@ PROTOTYPES = {
     "hpfg_upsample2x_bwd_sums": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _p]),
     "hpfg_upsample2x_bwd_blocks": (_i, [_i, _i, _i, _i]),
     "hpfg_loss_blocks": (_i, [_i, _i, _i]),
+    "hpfg_loss_nsum": (_i, [_i]),
     "hpfg_seg_loss_partials": (_i, [C.POINTER(LossArgs), _p]),
     "hpfg_seg_loss_finalize": (_i, [C.POINTER(LossArgs), _p]),
     "hpfg_seg_loss_bwd": (_i, [C.POINTER(LossArgs), _p, _p]),

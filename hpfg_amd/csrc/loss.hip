@@ -14,6 +14,7 @@
 #include <string.h>
 #include "common.h"
 #include "peer.h"
+#include "loss_wide.h"
 
 namespace {
 
@@ -276,9 +277,12 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(HpfgLossArgs a, long npix
 
 extern "C" int hpfg_loss_blocks(int N, int H, int W) { return (int)(((long)N * H * W + PIX_PER_BLOCK - 1) / PIX_PER_BLOCK); }
 
+// floats of one row of `partials` and of `sums`: the layout above for C <= 4, the wide family's (loss_wide.hip) for 5 <= C <= 16
+extern "C" int hpfg_loss_nsum(int C) { return C <= 4 ? HPFG_LOSS_NSUM : HPFG_LOSS_NSUM_WIDE; }
+
 static int check_loss(const HpfgLossArgs* a) {
   HPFG_ARG_CHECK(a && a->logits && a->coef && a->sums, "seg_loss: null pointer");
-  HPFG_ARG_CHECK(a->C >= 2 && a->C <= 4, "seg_loss: C must be 2..4 (got %d)", a->C);
+  HPFG_ARG_CHECK(a->C >= 2 && a->C <= 16, "seg_loss: C must be 2..16 (got %d)", a->C);
   HPFG_ARG_CHECK(a->N > 0 && a->n_lab >= 0 && a->n_lab <= a->N && a->H > 0 && a->W > 0 && a->world >= 1, "seg_loss: bad sizes");
   HPFG_ARG_CHECK(a->n_lab == 0 || a->labels0, "seg_loss: labels0 missing");
   return 0;
@@ -288,6 +292,7 @@ static int loss_partials_impl(const HpfgLossArgs* a, const HpfgPeerX* px, void* 
   if (int rc = check_loss(a)) return rc;
   HPFG_ARG_CHECK(a->partials, "seg_loss_partials: workspace missing");
   int nblk = hpfg_loss_blocks(a->N, a->H, a->W);
+  if (a->C > 4) return hpfg_loss_wide_partials(a, px, nblk, stream);
   if (a->C == 4) hipLaunchKernelGGL(loss_partials_kernel<4>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, *a, (long)a->H * a->W);
   else if (a->C == 3) hipLaunchKernelGGL(loss_partials_kernel<3>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, *a, (long)a->H * a->W);
   else hipLaunchKernelGGL(loss_partials_kernel<2>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, *a, (long)a->H * a->W);
@@ -303,6 +308,7 @@ extern "C" int hpfg_seg_loss_partials_x(const HpfgLossArgs* a, const HpfgPeerX* 
   HPFG_ARG_CHECK(px, "seg_loss_partials_x: null exchange descriptor");
   if (px->world > 1) {
     HPFG_ARG_CHECK(px->world <= HPFG_PEER_MAX_RANKS && px->rank >= 0 && px->rank < px->world && px->epoch && px->slot >= 0 && NS <= px->cap &&
+                       (!a || hpfg_loss_nsum(a->C) <= px->cap) &&
                        px->slot_bytes == hpfg_peer_slot_bytes(px->world, px->cap),
                    "seg_loss_partials_x: bad exchange descriptor");
     for (int r = 0; r < px->world; ++r) HPFG_ARG_CHECK(px->mbox[r], "seg_loss_partials_x: mailbox of rank %d not mapped", r);
@@ -313,6 +319,7 @@ extern "C" int hpfg_seg_loss_partials_x(const HpfgLossArgs* a, const HpfgPeerX* 
 extern "C" int hpfg_seg_loss_finalize(const HpfgLossArgs* a, void* stream) {
   if (int rc = check_loss(a)) return rc;
   HPFG_ARG_CHECK(a->out, "seg_loss_finalize: out missing");
+  if (a->C > 4) return hpfg_loss_wide_finalize(a, stream);
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a);
   return hpfg_launch_status("loss_finalize_kernel");
 }
@@ -323,6 +330,7 @@ extern "C" int hpfg_seg_loss_bwd(const HpfgLossArgs* a, const float* grad_scale_
   long total = (long)a->N * a->H * a->W;
   long b = (total + 255) / 256;
   if (b > 4096) b = 4096;
+  if (a->C > 4) return hpfg_loss_wide_bwd(a, grad_scale_dev, (int)b, stream);
   if (a->C == 4) hipLaunchKernelGGL(loss_bwd_kernel<4>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, *a, (long)a->H * a->W, grad_scale_dev);
   else if (a->C == 3) hipLaunchKernelGGL(loss_bwd_kernel<3>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, *a, (long)a->H * a->W, grad_scale_dev);
   else hipLaunchKernelGGL(loss_bwd_kernel<2>, dim3((int)b), dim3(256), 0, (hipStream_t)stream, *a, (long)a->H * a->W, grad_scale_dev);

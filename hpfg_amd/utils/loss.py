@@ -38,13 +38,16 @@ class _SegLossFn(torch.autograd.Function):
         lib = L.load()
         if not logits.is_cuda:
             raise RuntimeError("hpfg_amd losses run on the HIP library only (no CPU fallback)")
+        if logits.shape[1] > L.LOSS_MAX_CLASSES:          # (before the first launch: the layout conversion below may be one)
+            raise ValueError(f"seg_loss supports at most {L.LOSS_MAX_CLASSES} classes (got {logits.shape[1]})")
         x = _nhwc(logits.float())
         N, H, W, Cc = x.shape
         dev = x.device
         a = L.LossArgs()
         nblk = lib.hpfg_loss_blocks(N, H, W)
-        partials = torch.empty(nblk * L.LOSS_NSUM, dtype=torch.float32, device=dev)
-        sums = torch.empty(L.LOSS_NSUM, dtype=torch.float32, device=dev)
+        nsum = lib.hpfg_loss_nsum(Cc)
+        partials = torch.empty(nblk * nsum, dtype=torch.float32, device=dev)
+        sums = torch.empty(nsum, dtype=torch.float32, device=dev)
         out = torch.empty(8, dtype=torch.float32, device=dev)
         t = _nhwc(t_logits.float()) if t_logits is not None else None
         a.logits, a.t_logits, a.labels0, a.labels1 = L.ptr(x), L.ptr(t), L.ptr(labels0), L.ptr(labels1)

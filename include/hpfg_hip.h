@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 133
+#define HPFG_VERSION 134
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -351,8 +351,8 @@ typedef struct HpfgLossArgs {
   const uint8_t* labels0;   /* labels for images [0,n_lab) (255 = ignore), group 0 */
   const uint8_t* labels1;   /* (pseudo-)labels for images [n_lab,N), group 1, or NULL */
   const float* coef;        /* device [8]: ce0, dice0, ce1, dice1, mse_w, 0,0,0  (per-step weights live on the device) */
-  float* partials;          /* workspace [hpfg_loss_blocks()][HPFG_LOSS_NSUM] */
-  float* sums;              /* out [HPFG_LOSS_NSUM] reduced sums (all-reduce these for data parallel) */
+  float* partials;          /* workspace [hpfg_loss_blocks()][hpfg_loss_nsum(C)] */
+  float* sums;              /* out [hpfg_loss_nsum(C)] reduced sums (all-reduce these for data parallel) */
   float* out;               /* out [8]: total, ce0, dice0, ce1, dice1, mse, 0, 0 */
   float* dlogits;           /* backward output [N,H,W,C] */
   int32_t N, n_lab, H, W, C;
@@ -364,8 +364,10 @@ typedef struct HpfgLossArgs {
   const float* cons_mask;   /* [N-n_lab][H][W] 0/1 weights of the consistency term, or NULL.  With a mask the term is
                                sum(mask * d^2) / (2*sum(mask) + 1e-16)  (UAMT, 2019_07...Uncertainty_Aware...py:160-164) instead of the mean */
 } HpfgLossArgs;
-#define HPFG_LOSS_NSUM 32
+#define HPFG_LOSS_NSUM 32           /* C <= 4 */
+#define HPFG_LOSS_NSUM_WIDE 104     /* 5 <= C <= 16: six scalars (+2 unused), then I0, Z0, Y0, I1, Z1, Y1 in blocks of 16 (csrc/loss_wide.hip) */
 int hpfg_loss_blocks(int N, int H, int W);
+int hpfg_loss_nsum(int C);          /* floats per row of `partials` and in `sums`: HPFG_LOSS_NSUM for C <= 4, HPFG_LOSS_NSUM_WIDE above */
 int hpfg_seg_loss_partials(const HpfgLossArgs* a, void* stream);   /* softmax + CE/Dice/MSE partial sums */
 int hpfg_seg_loss_partials_x(const HpfgLossArgs* a, const HpfgPeerX* px, void* stream);   /* + the cross-rank sum of `sums` (peer mailbox) */
 int hpfg_seg_loss_finalize(const HpfgLossArgs* a, void* stream);   /* sums -> loss scalars (device) */
