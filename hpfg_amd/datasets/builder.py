@@ -8,7 +8,7 @@ pipelines) are outside the hot-path build and raise NotImplementedError like an 
 """
 from .synthetic import get_ssl_synthetic_loader, get_synthetic_loader, synth_batch
 
-_REAL = {"lidc", "synapse", "isic", "sup_lidc", "sup_synapse", "sup_isic", "sup_building"}
+_REAL = {"lidc", "isic", "sup_lidc", "sup_isic", "sup_building"}
 
 
 def _device_synthetic(args, rank):
@@ -45,6 +45,13 @@ def build_loader(args, rank: int = 0):
     if args.datasets == "sup_acdc":      # builder.py:45-50
         from .acdc import get_acdc_loader
         return get_acdc_loader(root=args.data_path, train_crop_size=args.train_crop_size, batch_size=args.batch_size, device=getattr(args, "device", "cuda"))
+    if args.datasets == "synapse":       # builder.py:27-34: Synapse npz slices from disk, the same pool and augmentation
+        from .synapse import get_ssl_synapse_loader
+        return get_ssl_synapse_loader(root=args.data_path, train_crop_size=args.train_crop_size, batch_size=args.batch_size,
+                                      unlabel_batch_size=args.unlabel_batch_size, label_num=args.label_num, device=getattr(args, "device", "cuda"))
+    if args.datasets == "sup_synapse":   # builder.py:58-62
+        from .synapse import get_synapse_loader
+        return get_synapse_loader(root=args.data_path, train_crop_size=args.train_crop_size, batch_size=args.batch_size, device=getattr(args, "device", "cuda"))
     if args.datasets in _REAL:
         raise NotImplementedError(f"dataset '{args.datasets}' (real-data I/O) is outside the MI355X hot-path build; "
                                   f"use 'synthetic' / 'sup_synthetic' (same batch contract)")

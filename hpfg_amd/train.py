@@ -1024,8 +1024,9 @@ class _Best:
         return getattr(self.args, self.path_attr, None) if self.path_attr else None
 
     def __call__(self, model, optimizer, lr_scheduler, test_loader, cur_itrs, name="test"):
-        from .val import test_acdc
-        dice, hd95 = test_acdc(model=model, test_loader=test_loader, args=self.args, cur_itrs=cur_itrs, name=name)
+        from .val import test_acdc, test_synapse
+        test = test_synapse if getattr(self.args, "datasets", None) in ("synapse", "sup_synapse") else test_acdc      # Synapse volumes: cubic-spline resize (val.py:196)
+        dice, hd95 = test(model=model, test_loader=test_loader, args=self.args, cur_itrs=cur_itrs, name=name)
         logger = getattr(self.args, "logger", None)
         if logger is not None:
             logger.info("{}_dice: {:.4f} {}_hd95: {:.4f}".format(self.key, dice, self.key, hd95))

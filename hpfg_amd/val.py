@@ -8,6 +8,10 @@ by construction), all slices go through the HIP engine in fixed-size batches, ar
 kernels, and only C*C integers per volume cross to the host.
 HD95 (medpy ``hd95``, CPU distance transforms; out of scope of the hot path) is reported as 0.0 unless
 ``with_hd95=True``, which runs the scipy restatement below on the host.
+
+``test_synapse`` / ``test_single_volume_synapse`` (val.py:196-265) are the same machinery behind the other resize of the reference: every
+Synapse slice goes to ``patch_size`` with ``zoom(order=3)``, a cubic B-spline.  ``resize_cubic`` does that for a whole volume on the device
+(hpfg_resize_cubic, csrc/resize.hip) from per-axis tap tables built here on the host in fp64; the resize back stays order 0.
 """
 from __future__ import annotations
 
@@ -47,14 +51,103 @@ def _resize_nearest(t: torch.Tensor, dst_hw: Sequence[int]) -> torch.Tensor:
     return out.reshape(s, int(dst_hw[0]), int(dst_hw[1]))
 
 
-def predict_volume(image: torch.Tensor, net, patch_size: Sequence[int] = (256, 256)) -> torch.Tensor:
-    """image [S,h,w] (float, any device) -> predicted labels uint8 [S,h,w] on the model's device."""
+_CUBIC_REACH = 16      # samples on either side of the four B-spline taps that a tap table keeps: |sqrt(3) - 2|^16 < 1e-9
+
+
+def _cubic_prefilter_matrix(n: int) -> np.ndarray:
+    """The cubic spline prefilter of scipy.ndimage (spline_filter1d, order 3, mode 'mirror') on a line of n samples as an n x n matrix,
+    fp64: gain (1 - z)(1 - 1/z) with the pole z = sqrt(3) - 2, the closed-form causal start under whole-sample mirror boundaries, the
+    causal recursion, the anti-causal start and the anti-causal recursion -- applied to the columns of the identity."""
+    z = np.sqrt(3.0) - 2.0
+    c = np.eye(n) * ((1.0 - z) * (1.0 - 1.0 / z))
+    zp = z ** np.arange(2 * n - 1, dtype=np.float64)
+    i = np.arange(1, n - 1)
+    c[0] = (c[0] + zp[n - 1] * c[n - 1] + ((zp[i] + zp[2 * n - 2 - i])[:, None] * c[i]).sum(0)) / (1.0 - zp[2 * n - 2])
+    for j in range(1, n):
+        c[j] += z * c[j - 1]
+    c[n - 1] = z / (z * z - 1.0) * (z * c[n - 2] + c[n - 1])
+    for j in range(n - 2, -1, -1):
+        c[j] = z * (c[j + 1] - c[j])
+    return c
+
+
+def _cubic_axis_matrix(n_in: int, n_out: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One axis of scipy.ndimage.zoom(a, n_out / n_in, order=3) with scipy's defaults as a matrix [n_out, n_in] (fp64), the floor of every
+    output coordinate, and scipy's own verdict on which outputs it computes at all: its last coordinate o * (n_in - 1) / (n_out - 1) can land a
+    rounding error beyond n_in - 1, and it then writes the constant 0 (at 512 -> 224, the Synapse case).  Like ``_zoom_index`` the verdict
+    is taken from scipy, not re-derived."""
+    from scipy.ndimage import zoom
+    x = np.arange(n_out, dtype=np.float64) * ((n_in - 1) / (n_out - 1))
+    f = np.floor(x)
+    t = x - f
+    w = np.stack([(1 - t) ** 3 / 6, (3 * t ** 3 - 6 * t ** 2 + 4) / 6, (-3 * t ** 3 + 3 * t ** 2 + 3 * t + 1) / 6, t ** 3 / 6], 1)
+    period = 2 * (n_in - 1)
+    idx = np.abs(f.astype(np.int64)[:, None] - 1 + np.arange(4)[None]) % period          # mirrored tap indices
+    idx = np.where(idx > n_in - 1, period - idx, idx)
+    valid = zoom(np.ones(n_in), n_out / n_in, order=3) > 0.5
+    assert valid.shape == (n_out,), (valid.shape, n_in, n_out)
+    m = (w[:, :, None] * _cubic_prefilter_matrix(n_in)[idx]).sum(1) * valid[:, None]
+    return m, f.astype(np.int64), valid
+
+
+@lru_cache(maxsize=64)
+def _cubic_axis_table(n_in: int, n_out: int) -> np.ndarray:
+    """The tap table of hpfg_resize_cubic for one axis (include/hpfg_hip.h): int32 words, float32 w[n_out][RESIZE_TAPS] then first[n_out].
+    Row o of the axis matrix is kept on the RESIZE_TAPS columns from first[o] = floor(x_o) - 1 - 16, moved inside the line at its ends (the
+    mirror images are already folded into the columns that exist), i.e. whole for n_in <= RESIZE_TAPS; what is cut off is below 1e-9."""
+    m, f, valid = _cubic_axis_matrix(n_in, n_out)
+    first = np.clip(f - 1 - _CUBIC_REACH, 0, max(n_in - L.RESIZE_TAPS, 0))
+    cols = first[:, None] + np.arange(L.RESIZE_TAPS)[None]
+    w = np.where(cols < n_in, np.take_along_axis(m, np.minimum(cols, n_in - 1), 1), 0.0)
+    assert float((np.abs(m).sum(1) - np.abs(w).sum(1)).max()) < 1e-9, (n_in, n_out)
+    return np.concatenate([w.astype(np.float32).reshape(-1).view(np.int32), np.where(valid, first, -1).astype(np.int32)])
+
+
+_cubic_dev = {}      # (n_in, n_out, device) -> tap table on the device; (device,) -> scratch buffer (grown on demand, reused by every call)
+
+
+def _cubic_table_dev(n_in: int, n_out: int, device) -> torch.Tensor:
+    key = (n_in, n_out, str(device))
+    if key not in _cubic_dev:
+        _cubic_dev[key] = torch.from_numpy(_cubic_axis_table(n_in, n_out)).to(device)
+    return _cubic_dev[key]
+
+
+def resize_cubic(t: torch.Tensor, dst_hw: Sequence[int]) -> torch.Tensor:
+    """[S,h,w] float32 on the device -> [S,H,W]: scipy.ndimage.zoom(slice, (H/h, W/w), order=3) of every slice (the reference's Synapse
+    evaluation resize, val.py:243) by hpfg_resize_cubic on the current stream.  A (h, w) == dst_hw input is returned as is."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+        raise ValueError("resize_cubic takes a float32 [S,h,w] tensor on the device (no CPU fallback)")
+    s, h, w = t.shape
+    H, W = int(dst_hw[0]), int(dst_hw[1])
+    if (h, w) == (H, W):
+        return t
+    lib = L.load()
+    need = lib.hpfg_resize_cubic_scratch_bytes(s, h, w, H, W)
+    if need < 0:
+        raise ValueError(f"resize_cubic: [{s},{h},{w}] -> [{H},{W}]: every axis needs 2 .. 8192 samples and S 1 .. 65535")
+    ty, tx = _cubic_table_dev(h, H, t.device), _cubic_table_dev(w, W, t.device)
+    scratch = _cubic_dev.get((str(t.device),))
+    if scratch is None or scratch.numel() < need:
+        scratch = _cubic_dev[(str(t.device),)] = torch.empty(need, dtype=torch.uint8, device=t.device)
+    src = t.contiguous()
+    out = torch.empty((s, H, W), dtype=torch.float32, device=t.device)
+    L.check(lib.hpfg_resize_cubic(L.ptr(src), s, h, w, L.ptr(out), H, W, L.ptr(ty), L.ptr(tx), L.ptr(scratch), scratch.numel(),
+                                  torch.cuda.current_stream(t.device).cuda_stream), "resize_cubic")
+    return out
+
+
+def predict_volume(image: torch.Tensor, net, patch_size: Sequence[int] = (256, 256), order: int = 0) -> torch.Tensor:
+    """image [S,h,w] (float, any device) -> predicted labels uint8 [S,h,w] on the model's device.  order: the spline order of the resize
+    to ``patch_size`` -- 0 (ACDC, val.py:274) or 3 (Synapse, val.py:243); the resize back is order 0 in both."""
+    if order not in (0, 3):
+        raise ValueError(f"predict_volume: spline order {order} (0 or 3)")
     dev = next(net.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("hpfg_amd.val runs on the HIP library only (no CPU fallback)")
     vol = image.to(dev, torch.float32)
     s, h, w = vol.shape
-    x = _resize_nearest(vol, patch_size)
+    x = resize_cubic(vol, patch_size) if order == 3 else _resize_nearest(vol, patch_size)
     was_training = net.training
     net.eval()
     fwd = net.val if hasattr(net, "val") else net
@@ -135,12 +228,29 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), with_h
 test_single_volume.__test__ = False      # reference name, not a pytest case
 
 
-def test_acdc(model, test_loader, args, cur_itrs=0, name="test", with_hd95: bool = False):
-    """Reference signature (val.py:154): mean foreground Dice and mean HD95 over the volumes of ``test_loader`` (bs=1 volumes
-    ``(image [1,S,h,w], label [1,S,h,w])``).  With ``args.writer`` (anything with TensorBoard's ``add_image``) the first volume's first slice
-    is logged the way main.py:309-325 does: ``<name>/Image`` (the slice resized to ``test_crop_size``, [1,H,W]), ``<name>/label_pred`` and
-    ``<name>/label_true`` (the dataset's ``label_to_img`` palette images, HWC) -- the prediction is slice 0 of the volume prediction above
-    (resize -> eval forward -> arg-max -> resize back: the arithmetic of the reference's separate forward of that slice)."""
+def test_single_volume_synapse(image, label, net, classes, patch_size=(256, 256), test_save_path=None, case=None, z_spacing=1, _pred_out: list = None):
+    """Reference signature (val.py:235).  image, label: [1,S,h,w], or [1,h,w] for the reference's 2-D branch (one slice, forwarded at its
+    own size).  Every slice whose size differs from ``patch_size`` is resized with the cubic spline (``resize_cubic`` = zoom(order=3),
+    val.py:243), forwarded, arg-maxed and resized back with order 0 (val.py:251).  Returns [(dice, hd95)] for classes 1..classes-1 with
+    hd95 = 0.0 as in ``test_single_volume``; ``test_save_path`` / ``case`` / ``z_spacing`` are unused there as well."""
+    dev = next(net.parameters()).device
+    img, lab = image.squeeze(0), label.squeeze(0).to(dev)
+    if img.dim() == 2:
+        pred = predict_volume(img.unsqueeze(0), net, tuple(img.shape))[0]
+    else:
+        pred = predict_volume(img, net, patch_size, order=3)
+    if _pred_out is not None:
+        _pred_out.append(pred if pred.dim() == 3 else pred.unsqueeze(0))
+    cm = confusion_counts(pred, lab.to(torch.uint8), classes)
+    return [(dice_from_counts(cm, c), 0.0) for c in range(1, classes)]
+
+
+test_single_volume_synapse.__test__ = False
+
+
+def _test_volumes(single_volume, test_loader, args, cur_itrs, name):
+    """The body ``test_acdc`` and ``test_synapse`` share (val.py:154-193, 196-232): the mean over the volumes of ``test_loader`` (bs=1 volumes
+    ``(image [1,S,h,w], label [1,S,h,w])``) of ``single_volume(image, label, keep)``, and the image hooks of the first volume."""
     metric_list = 0.0
     n = 0
     writer = getattr(args, "writer", None)
@@ -148,11 +258,10 @@ def test_acdc(model, test_loader, args, cur_itrs=0, name="test", with_hd95: bool
     for image, label in test_loader:
         hook = n == 0 and writer is not None and hasattr(writer, "add_image") and to_img is not None
         keep = [] if hook else None
-        metric_list = metric_list + np.array(test_single_volume(image, label, model, classes=args.num_classes,
-                                                               patch_size=args.test_crop_size, with_hd95=with_hd95, _pred_out=keep))
+        metric_list = metric_list + np.array(single_volume(image, label, keep))
         if hook:
             first = image[0, 0].to(keep[0].device, torch.float32)
-            shown = _resize_nearest(first.unsqueeze(0), args.test_crop_size)          # [1,H,W]: what the network saw
+            shown = _resize_nearest(first.unsqueeze(0), args.test_crop_size)          # [1,H,W], order 0 in both reference loops (val.py:178,215)
             writer.add_image("{}/Image".format(name), shown.cpu(), cur_itrs)
             writer.add_image("{}/label_pred".format(name), to_img(keep[0][0].cpu().numpy()), cur_itrs, dataformats="HWC")
             writer.add_image("{}/label_true".format(name), to_img(label[0, 0].cpu().numpy()), cur_itrs, dataformats="HWC")
@@ -164,4 +273,26 @@ def test_acdc(model, test_loader, args, cur_itrs=0, name="test", with_hd95: bool
     return float(np.mean(metric_list, axis=0)[0]), float(np.mean(metric_list, axis=0)[1])
 
 
+def test_acdc(model, test_loader, args, cur_itrs=0, name="test", with_hd95: bool = False):
+    """Reference signature (val.py:154): mean foreground Dice and mean HD95 over the volumes of ``test_loader`` (bs=1 volumes
+    ``(image [1,S,h,w], label [1,S,h,w])``).  With ``args.writer`` (anything with TensorBoard's ``add_image``) the first volume's first slice
+    is logged the way main.py:309-325 does: ``<name>/Image`` (the slice resized to ``test_crop_size``, [1,H,W]), ``<name>/label_pred`` and
+    ``<name>/label_true`` (the dataset's ``label_to_img`` palette images, HWC) -- the prediction is slice 0 of the volume prediction above
+    (resize -> eval forward -> arg-max -> resize back: the arithmetic of the reference's separate forward of that slice)."""
+    return _test_volumes(lambda image, label, keep: test_single_volume(image, label, model, classes=args.num_classes, patch_size=args.test_crop_size,
+                                                                       with_hd95=with_hd95, _pred_out=keep), test_loader, args, cur_itrs, name)
+
+
 test_acdc.__test__ = False
+
+
+def test_synapse(model, test_loader, args, cur_itrs=0, name="test"):
+    """Reference signature (val.py:196): ``test_acdc`` with ``test_single_volume_synapse`` per volume -- the slices reach the network through
+    the cubic-spline resize.  The image hooks are those of ``test_acdc`` (the shown slice is resized with order 0 there too, val.py:215); the
+    logged prediction is slice 0 of the scored volume prediction."""
+    return _test_volumes(lambda image, label, keep: test_single_volume_synapse(image, label, model, classes=args.num_classes,
+                                                                               patch_size=args.test_crop_size, _pred_out=keep),
+                         test_loader, args, cur_itrs, name)
+
+
+test_synapse.__test__ = False

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 134
+#define HPFG_VERSION 135
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -378,6 +378,19 @@ int hpfg_argmax_labels(const float* logits, int N, int H, int W, int C, const ui
 /* evaluation (val.py:376-387, medpy binary dc): counts[gt*C + pred] += 1 over n voxels (labels >= C are ignored); the caller
  * zeroes `counts` (C*C uint64) and derives per-class Dice = 2*n(A&B) / (n(A) + n(B)) from rows / columns */
 int hpfg_confusion_counts(const uint8_t* pred, const uint8_t* gt, long n, int C, unsigned long long* counts, void* stream);
+/* evaluation of Synapse volumes (val.py:243: zoom(slice, (patch/x, patch/y), order=3) of every slice on the host): the cubic B-spline resize
+ * src [S][h][w] -> dst [S][H][W] (fp32, contiguous) of all slices of a volume in one call.  Spline prefilter (pole sqrt(3) - 2, mirror
+ * boundaries) and interpolation are linear and separable, and the prefilter's response decays below 1e-9 within 16 samples: per axis, output
+ * o is sum_t w[o][t] * in[first[o] + t] over HPFG_RESIZE_TAPS (= 4 + 2 * 16) input samples.  The caller builds that table on the host
+ * (hpfg_amd/val.py::_cubic_axis_table, fp64) and passes it per axis, n_out * (HPFG_RESIZE_TAPS + 1) 4-byte words on the device:
+ *   float w[n_out][HPFG_RESIZE_TAPS], then int32 first[n_out]; first[o] + min(HPFG_RESIZE_TAPS, n_in) <= n_in (taps beyond n_in carry weight 0),
+ *   first[o] < 0: out[o] = 0 -- scipy writes its constant there (a last coordinate that lands a rounding error past n_in - 1).
+ * taps_y: h -> H, taps_x: w -> W (16-byte aligned).  The axis-0 pass writes [S][H][w] floats into `scratch`
+ * (hpfg_resize_cubic_scratch_bytes(); -1 for sizes the call refuses: an axis shorter than 2 or longer than 8192, S > 65535). */
+#define HPFG_RESIZE_TAPS 36
+int hpfg_resize_cubic(const float* src, int S, int h, int w, float* dst, int H, int W, const float* taps_y, const float* taps_x, void* scratch,
+                      long scratch_bytes, void* stream);
+long hpfg_resize_cubic_scratch_bytes(int S, int h, int w, int H, int W);
 /* Training-time slice augmentation on the device (datasets/utils.py:73-117 RandomGenerator.__call__: random_rot_flip | random_rotate,
  * then scipy zoom(order=0) to the network size, image and mask alike).  The host draws the random parameters in the reference's
  * order and supplies, per sample, the source slice, the rot90/flip or rotation parameters (rotation matrix and offset exactly
