@@ -111,7 +111,7 @@ class _UNetFn(torch.autograd.Function):
         # tools/nested_fork_probe.py): only the single trainable network of a step (it runs on the origin stream) takes the bucketed path;
         # the others are exchanged once after both backward passes have joined (_StepBase._reduce_grads).
         nested = getattr(dp, "p2p_grads", False) and not getattr(net, "_alone", False)
-        if dp is not None and dp.active and getattr(dp, "overlap", False) and getattr(eng, "direct", False) and not nested:
+        if dp is not None and dp.active and getattr(dp, "overlap", False) and eng.direct and not nested:
             # data parallel: hand each finished slice of the flat gradient buffer to the all-reduce while backward continues
             cb = lambda i: dp.launch_bucket(net.grad_bucket(i))
             net._buckets_launched = True
@@ -287,9 +287,9 @@ class UNet(nn.Module):
         key = (tuple(x.shape), x.device.index)
         pool = self._engines.setdefault(key, [])
         direct = bool(getattr(self, "direct_grads", False))
-        eng = next((e for e in pool if not e.bwd_ready and getattr(e, "direct", False) == direct), None)
+        eng = next((e for e in pool if not e.bwd_ready and e.direct == direct), None)
         if eng is None and len(pool) >= 4:
-            eng = next((e for e in pool if getattr(e, "direct", False) == direct), None)   # graphs never back-propagated are dropped
+            eng = next((e for e in pool if e.direct == direct), None)   # graphs never back-propagated are dropped
         if eng is None:
             named = dict(self.named_parameters())
             params = {n: p.data for n, p in named.items()}
@@ -322,7 +322,7 @@ class UNet(nn.Module):
         return eng
 
     def _accumulate_grads(self, eng: E.UNetEngine):
-        if getattr(eng, "direct", False):      # backward wrote straight into the flat gradient buffer
+        if eng.direct:      # backward wrote straight into the flat gradient buffer
             self.attach_grad_views()
             return
         n = self._backbone_numel

@@ -205,3 +205,61 @@ def test_driver_loop_iteration_law_evaluation_cadence_and_label_cycling():
     assert losses.tolist() == [float(k) for k in range(1, 9)]
     run.drive(unlabel, _with_labels(label), None, [(best, "m", "o", "s", "model")])
     assert len(evals) == 4                                                   # no test loader: no evaluation
+
+
+def test_bn_route_truth_table():
+    """engine.bn_route over every combination of its six inputs, against the predicates the engine's passes used to spell out at each use."""
+    import itertools
+
+    from hpfg_amd import _lib as L
+    from hpfg_amd.engine import ACC, ALLREDUCE, EVAL, LOCAL, PEER, bn_route
+    n = 0
+    for train, math, acc_on, peer, world, force in itertools.product((False, True), (L.MATH_F32, L.MATH_BF16X3), (False, True), (False, True),
+                                                                     (1, 2, 8), (False, True)):
+        sync = world > 1 or force
+        if not train:
+            want = EVAL
+        elif acc_on and math == L.MATH_BF16X3 and not peer and not sync:
+            want = ACC
+        elif peer and sync:
+            want = PEER
+        elif sync:
+            want = ALLREDUCE
+        else:
+            want = LOCAL
+        assert bn_route(train, math, acc_on, peer, world, force) == want, (train, math, acc_on, peer, world, force)
+        n += 1
+    assert n == 96 and len({ACC, LOCAL, ALLREDUCE, PEER, EVAL}) == 5
+    assert bn_route(True, L.MATH_BF16X3, True, False, 1, False) == ACC
+    assert bn_route(True, L.MATH_BF16X3, True, True, 1, False) == LOCAL          # a peer context without sync: neither exchange nor accumulators
+    assert bn_route(True, L.MATH_BF16X3, True, True, 2, False) == PEER and bn_route(True, L.MATH_BF16X3, True, True, 1, True) == PEER
+    assert bn_route(True, L.MATH_BF16X3, True, False, 1, True) == ALLREDUCE
+    for acc_on, peer, world, force in itertools.product((False, True), (False, True), (1, 2), (False, True)):
+        assert bn_route(True, L.MATH_F32, acc_on, peer, world, force) != ACC        # the accumulators serve the bf16x3 kernels only
+        assert bn_route(False, L.MATH_BF16X3, acc_on, peer, world, force) == EVAL
+
+
+def test_desc_table_sub_ranges_alias_the_host_array():
+    """engine.DescTable on a CPU tensor: sub(lo, hi) = (device pointer of descriptor lo, host view of [lo, hi) that is NOT a copy, hi - lo)."""
+    import ctypes as C
+
+    from hpfg_amd import _lib as L
+    from hpfg_amd.engine import DescTable
+    descs = (L.SlabDesc * 5)()
+    for i, d in enumerate(descs):
+        d.S, d.taps, d.Cout = 10 + i, 9, 16
+    t = DescTable(descs, torch.device("cpu"))
+    sz = C.sizeof(L.SlabDesc)
+    assert t.host is descs and t.dev.device.type == "cpu" and t.dev.numel() == 5 * sz
+    assert bytes(t.dev.numpy().tobytes()) == bytes(descs)          # the device copy holds the descriptors as built
+    base = t.dev.data_ptr()
+    for lo, hi in ((0, 5), (1, 4), (3, 5), (2, 3)):
+        ptr, host, n = t.sub(lo, hi)
+        assert ptr == base + lo * sz and n == hi - lo and len(host) == n and isinstance(host[0], L.SlabDesc)
+        assert [d.S for d in host] == [10 + i for i in range(lo, hi)]
+    _, host, _ = t.sub(1, 4)
+    host[2].S = 77                                   # written through the view ...
+    assert descs[3].S == 77                          # ... it shows in the parent array
+    descs[1].Cout = 32
+    assert host[0].Cout == 32
+    assert C.addressof(host) == C.addressof(descs) + sz
