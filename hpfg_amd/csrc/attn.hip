@@ -1,6 +1,9 @@
 // Attention core of the SegFormer branch on the matrix cores (reference model/segformer.py:92-128, Attention.forward after the q / kv
 // projections and the spatial reduction):   out = softmax(scale * q k^T) v   per (image, head), head dim D = 32 or 64 (every kernel is a template over D), at most 64 keys.
 //
+// (65 .. 256 keys -- inputs above 256 x 256 -- are served by attn_keys.hip, which walks the keys in blocks of 64 with the LDS images and fragment
+// helpers of this file: attn_frag.h holds what the two share.)
+//
 // Every product is split-bf16 ("bf16x3": hi*hi + hi*lo + lo*hi, fp32 accumulate) on v_mfma_f32_16x16x32_bf16, like the convolutions.
 // Head dim 32 is exactly one MFMA k-step, so a 16 x 16 score tile costs three MFMAs; head dim 64 (MiT-B1 and wider) is two k-steps, six
 // MFMAs, and P V / dS K / dV / dK produce four 16-row d-tiles instead of two.  Two facts keep the kernels free of LDS transposes of the
@@ -22,112 +25,9 @@
 // counter was read for these kernels.  Not analysed at all: the 2-byte scalar stores that write a transposed image in stage_kv (stride
 // TROW between a thread's 8 stores; one pass at D = 32, two at D = 64) -- staging runs once per workgroup.  The 16-byte pad stays at D = 64
 // on that reasoning; what was measured is the kernels' time against equal-work D = 32 launches.
-#include "common.h"
+#include "attn_frag.h"
 
 namespace {
-
-typedef __bf16 a_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 a_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 a_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float a_f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int MK = 64;                         // maximum keys
-constexpr int TROW = 144;                      // bytes per row of a [D d][64 keys] bf16 image (128 B + 16 B pad)
-constexpr int QROW = 80;                       // bytes per row of a per-wave [D d][32 q] bf16 image (64 B + 16 B pad)
-template <int D> struct Geo {
-  static_assert(D == 32 || D == 64, "head dim 32 or 64");
-  static constexpr int KS = D / 32, DT = D / 16;          // MFMA k-steps over the head dim, 16-row d-tiles
-  static constexpr int KROW = 2 * D + 16;                  // bytes per row of a [64 keys][D d] bf16 image (+ 16 B pad)
-  static constexpr int KPLANE = MK * KROW, TPL = D * TROW, QPL = D * QROW;
-};
-constexpr float NEG = -3.0e38f;
-
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& hw, uint32_t& lw) {
-  const a_bf16x2 h = __builtin_convertvector(a_f32x2{x0, x1}, a_bf16x2);
-  hw = __builtin_bit_cast(uint32_t, h);
-  const a_f32x2 hf = {__builtin_bit_cast(float, hw << 16), __builtin_bit_cast(float, hw & 0xFFFF0000u)};
-  lw = __builtin_bit_cast(uint32_t, __builtin_convertvector(a_f32x2{x0, x1} - hf, a_bf16x2));
-}
-__device__ __forceinline__ void split8v(const float (&v)[8], a_bf16x8& hi, a_bf16x8& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) split2(v[2 * k], v[2 * k + 1], h[k], l[k]);
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  hi = __builtin_bit_cast(a_bf16x8, (u32x4{h[0], h[1], h[2], h[3]}));
-  lo = __builtin_bit_cast(a_bf16x8, (u32x4{l[0], l[1], l[2], l[3]}));
-}
-
-#define ATT_MFMA3(ACC, AH, AL, BH, BL)                                \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, BH, ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AL, BH, ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, BL, ACC, 0, 0, 0);
-
-// rows [key][D d] of k or v (which = 0 / 1) of one (image, head) -> natural image [64][D] (hi, lo) and / or transposed image [D][64]
-template <int D>
-__device__ __forceinline__ void stage_kv(const float* __restrict__ kv, int b, int h, int M, int C, int which, unsigned char* nat, unsigned char* trn, int tid) {
-  constexpr int KROW = Geo<D>::KROW, KPLANE = Geo<D>::KPLANE, TPL = Geo<D>::TPL;
-#pragma unroll
-  for (int chunk = tid; chunk < MK * D / 8; chunk += 256) {      // 8 head-dim values per thread and pass: one pass at D = 32, two at 64
-    const int key = chunk / (D / 8), d0 = (chunk % (D / 8)) * 8;
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (key < M) {
-      const float* p = kv + (((long)b * M + key) * 2 + which) * C + h * D + d0;
-      const f32x4 a = *reinterpret_cast<const f32x4*>(p), c = *reinterpret_cast<const f32x4*>(p + 4);
-      v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = c[0]; v[5] = c[1]; v[6] = c[2]; v[7] = c[3];
-    }
-    a_bf16x8 hi, lo;
-    split8v(v, hi, lo);
-    if (nat) {
-      *reinterpret_cast<a_bf16x8*>(nat + key * KROW + d0 * 2) = hi;
-      *reinterpret_cast<a_bf16x8*>(nat + key * KROW + d0 * 2 + KPLANE) = lo;
-    }
-    if (trn) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        *reinterpret_cast<__bf16*>(trn + (d0 + j) * TROW + key * 2) = hi[j];
-        *reinterpret_cast<__bf16*>(trn + (d0 + j) * TROW + key * 2 + TPL) = lo[j];
-      }
-    }
-  }
-}
-
-// fragment of a natural [rows][D d] image for k-step ks: row = row0 + (lane & 15), 8 consecutive d of k-group lane >> 4 (d = 32 ks + 8 g ..)
-template <int D>
-__device__ __forceinline__ a_bf16x8 nat_frag(const unsigned char* plane, int row0, int ks, int lane) {
-  return *reinterpret_cast<const a_bf16x8*>(plane + (row0 + (lane & 15)) * Geo<D>::KROW + ks * 64 + (lane >> 4) * 16);
-}
-// fragment of a transposed [D d][64 pos] image for contraction step s over 32 positions, in the accumulator-operand order: this lane's
-// positions are 32 s + 4 g + {0..3} and 32 s + 16 + 4 g + {0..3} (g = lane >> 4), row = d0 + (lane & 15)
-__device__ __forceinline__ a_bf16x8 trn_frag(const unsigned char* plane, int rowbytes, int d0, int s, int lane) {
-  const unsigned char* p = plane + (d0 + (lane & 15)) * rowbytes + (32 * s + 4 * (lane >> 4)) * 2;
-  const a_bf16x4 a = *reinterpret_cast<const a_bf16x4*>(p), b = *reinterpret_cast<const a_bf16x4*>(p + 32);
-  return a_bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-
-// this lane's 8 head-dim values of k-step ks (k-group lane >> 4) of row `row` of a [.., heads, D] tensor, times `mul`; zeros beyond `nrows`
-template <int D>
-__device__ __forceinline__ void load_row8(const float* __restrict__ base, long row, long nrows, int C, int h, int ks, int lane, float mul, float (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = 0.f;
-  if (row < nrows) {
-    const float* p = base + row * C + h * D + ks * 32 + (lane >> 4) * 8;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), c = *reinterpret_cast<const f32x4*>(p + 4);
-    v[0] = a[0] * mul; v[1] = a[1] * mul; v[2] = a[2] * mul; v[3] = a[3] * mul;
-    v[4] = c[0] * mul; v[5] = c[1] * mul; v[6] = c[2] * mul; v[7] = c[3] * mul;
-  }
-}
-
-// one row's D values as the split-bf16 fragments of its KS k-steps
-template <int D>
-__device__ __forceinline__ void load_row_frags(const float* __restrict__ base, long row, long nrows, int C, int h, int lane, float mul,
-                                               a_bf16x8 (&hi)[Geo<D>::KS], a_bf16x8 (&lo)[Geo<D>::KS]) {
-#pragma unroll
-  for (int ks = 0; ks < Geo<D>::KS; ++ks) {
-    float v[8];
-    load_row8<D>(base, row, nrows, C, h, ks, lane, mul, v);
-    split8v(v, hi[ks], lo[ks]);
-  }
-}
 
 // S^T tiles (keys on rows) of 16 queries -> probabilities p[t][r] of key 16 t + 4 g + r for the query on this lane (lane & 15)
 template <int D>
@@ -164,12 +64,6 @@ __device__ __forceinline__ void softmax_t(const unsigned char* ldsK, const a_bf1
   const float inv = 1.f / den;
 #pragma unroll
   for (int t = 0; t < 4; ++t) p[t] *= inv;
-}
-
-// accumulator tiles (2 s, 2 s + 1) -> split-bf16 B operand of contraction step s
-__device__ __forceinline__ void acc_operand(const f32x4& a, const f32x4& b, a_bf16x8& hi, a_bf16x8& lo) {
-  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  split8v(v, hi, lo);
 }
 
 template <int D>

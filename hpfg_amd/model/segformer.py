@@ -10,7 +10,9 @@ Same module tree, parameter names and constructor order as the reference's ``mod
     stride, so it is a GEMM over non-overlapping patches), the patch embeddings (after a HIP im2col), the head's per-stage projections and
     its 1x1 fuse / prediction convs.  No rocBLAS / hipBLASLt call is left (HPFG_MATH=f32 switches them to the exact-fp32 MFMA GEMM);
   - the attention core softmax(q k^T / sqrt(d)) v on the matrix cores (``csrc/attn.hip``: at most 64 keys after the spatial reduction,
-    head dim 32 = one MFMA k-step (B0) or 64 = two (B1); forward, dQ and dK / dV kernels without LDS transposes of the probabilities);
+    i.e. inputs up to 256 x 256; ``csrc/attn_keys.hip``: 65 to 256 keys in blocks of 64, inputs up to 512 x 512 -- ``attention_for`` picks
+    by the key count alone; head dim 32 = one MFMA k-step (B0) or 64 = two (B1); forward, dQ and dK / dV kernels without LDS transposes
+    of the probabilities);
   - every LayerNorm, depthwise 3x3 + GELU of the Mix-FFN, the head's bilinear resizes and its BatchNorm(train) + ReLU + Dropout2d,
     im2col / col2im of the overlap patch embeddings, residual adds with their drop-path factor (``csrc/tokens.hip``);
 * the head never builds the 4E-channel concat: ``linear_fuse`` (bias-free 1x1 conv) is applied per stage at the stage's resolution and the four
@@ -31,10 +33,29 @@ import torch
 import torch.nn as nn
 
 from .. import heads
-from ..ops_tokens import attention, bn_relu_dropout, dwconv_gelu, im2col, layer_norm, linear, residual_scale, resize_bilinear, resize_sum
+from ..ops_tokens import MAX_KEYS_LONG, attention_for, bn_relu_dropout, dwconv_gelu, im2col, layer_norm, linear, residual_scale, resize_bilinear, resize_sum
 
 MIT_SETTINGS = {"B0": [[32, 64, 160, 256], [2, 2, 2, 2]], "B1": [[64, 128, 320, 512], [2, 2, 2, 2]]}
 HEADS, SR = [1, 2, 5, 8], [8, 4, 2, 1]
+
+
+def stage_keys(height: int, width: int) -> list:
+    """Keys of the four MiT stages' attention for an input of this size: the stage map (patch embeddings 7/4, 3/2, 3/2, 3/2 with padding
+    k // 2) after the spatial reduction by SR.  (H / 32) (W / 32) in every stage when the sides are multiples of 32."""
+    keys, h, w = [], (int(height) - 1) // 4 + 1, (int(width) - 1) // 4 + 1
+    for i, s in enumerate(SR):
+        if i:
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        keys.append((h // s) * (w // s))
+    return keys
+
+
+def check_image_size(who: str, height: int, width: int) -> None:
+    """Raise before any launch when a stage of this input has more keys than the attention kernels take."""
+    keys = stage_keys(height, width)
+    if max(keys) > MAX_KEYS_LONG:
+        raise ValueError(f"{who}: a {int(height)} x {int(width)} input has {max(keys)} keys per attention row after the spatial reduction; the "
+                         f"attention kernels take at most {MAX_KEYS_LONG} (the 512x512 limit: inputs up to 512 x 512 pixels)")
 
 
 class Attention(nn.Module):
@@ -58,7 +79,7 @@ class Attention(nn.Module):
             x = linear(p, self.sr.weight.permute(0, 2, 3, 1).reshape(C, s * s * C), self.sr.bias)
             x = layer_norm(x, self.norm.weight, self.norm.bias)
         kv = linear(x, self.kv.weight, self.kv.bias)
-        return linear(attention(q, kv, self.head, self.scale), self.proj.weight, self.proj.bias)
+        return linear(attention_for(kv.shape[1])(q, kv, self.head, self.scale), self.proj.weight, self.proj.bias)
 
 
 class DWConv(nn.Module):
@@ -239,6 +260,7 @@ class SegFormerHead(nn.Module):
 class SegFormer(nn.Module):
     def __init__(self, image_size=(224, 224), in_channels=3, num_classes=4, model_name: str = "B0"):
         super().__init__()
+        check_image_size("SegFormer", *image_size)
         self.encoder = MiT(model_name=model_name, in_channels=in_channels)
         self.decoder = SegFormerHead(self.encoder.embed_dims, image_size=image_size, embed_dim=256, num_classes=num_classes)
         self.external_draws = None        # (drop_path_draws, dropout_mask): replay given random draws (tests)
@@ -246,6 +268,7 @@ class SegFormer(nn.Module):
     def forward(self, x):
         if not x.is_cuda:
             raise RuntimeError("hpfg_amd.SegFormer runs on the GPU only: its LayerNorm / attention / DWConv kernels have no CPU fallback")
+        check_image_size("SegFormer", x.shape[-2], x.shape[-1])
         dp, mask = self.external_draws if self.external_draws is not None else (None, None)
         return self.decoder(self.encoder(x.float(), dp), mask)
 
@@ -273,6 +296,7 @@ class SegFormer_Plus(nn.Module):
         if min(side) < NECK_POOL:
             raise ValueError(f"SegFormer_Plus: image size {list(image_size)} gives a {side[0]} x {side[1]} stage-4 map, smaller than the necks' "
                              f"{NECK_POOL} x {NECK_POOL} adaptive pooling; image sides must be at least {32 * NECK_POOL}")
+        check_image_size("SegFormer_Plus", *image_size)
         self.encoder = MiT(model_name=model_name, in_channels=in_channels)
         self.decoder = SegFormerHead(self.encoder.embed_dims, image_size=image_size, embed_dim=256, num_classes=num_classes)
         self.dense_projection_high = _neck(self.encoder.embed_dims[-1], 2048)
@@ -290,6 +314,7 @@ class SegFormer_Plus(nn.Module):
         if x.shape[-2] // 32 < NECK_POOL or x.shape[-1] // 32 < NECK_POOL:
             raise ValueError(f"SegFormer_Plus: a {x.shape[-2]} x {x.shape[-1]} input gives a stage-4 map smaller than the necks' {NECK_POOL} x "
                              f"{NECK_POOL} adaptive pooling; image sides must be at least {32 * NECK_POOL}")
+        check_image_size("SegFormer_Plus", x.shape[-2], x.shape[-1])
         dp, mask = self.external_draws if self.external_draws is not None else (None, None)
         feats = self.encoder(x.float(), dp)
         return self.decoder(feats, mask), feats[-1]

@@ -133,6 +133,65 @@ def attention(q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float) -> to
     return _Attention.apply(q, kv, heads, scale)
 
 
+MAX_KEYS_LONG = 256          # what csrc/attn_keys.hip walks in blocks of 64 (hpfg_attn_keys_max()): the keys of a MiT stage at 512 x 512
+_MATH_CODE = {"f32": 0, "bf16x3": 1}          # HPFG_MATH_F32 / HPFG_MATH_BF16X3 of include/hpfg_hip.h
+
+
+class _AttentionKeys(torch.autograd.Function):
+    """softmax(scale q k^T) v over up to MAX_KEYS_LONG keys (csrc/attn_keys.hip): the forward keeps out and the row log-sum-exp, the
+    backward rebuilds P = exp(S - lse) key block by key block.  Both math modes go through the same two entry points."""
+
+    @staticmethod
+    def forward(ctx, q, kv, heads, scale):
+        _need_gpu(q, "attention_keys")
+        lib = L.load()
+        qc, kvc = q.contiguous().float(), kv.contiguous().float()
+        B, N, C_ = qc.shape
+        M, d = kvc.shape[1], C_ // heads
+        out = torch.empty_like(qc)
+        lse = torch.empty(B, heads, N, dtype=torch.float32, device=q.device)
+        ctx.math = _MATH_CODE[gemm_math()]
+        L.check(lib.hpfg_attn_keys_fwd(L.ptr(qc), L.ptr(kvc), L.ptr(out), L.ptr(lse), B, N, M, heads, d, scale, ctx.math, _st(q)), "attn_keys_fwd")
+        ctx.save_for_backward(qc, kvc, out, lse)
+        ctx.heads, ctx.scale = heads, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        q, kv, out, lse = ctx.saved_tensors
+        B, N, C_ = q.shape
+        M, h = kv.shape[1], ctx.heads
+        d = C_ // h
+        do = dout.contiguous()
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        n_scr = lib.hpfg_attn_keys_scratch_floats(B, N, M, h, d, ctx.math)
+        if n_scr < 0:
+            L.check(-1, "attn_keys_scratch_floats")
+        scratch = torch.empty(n_scr, dtype=torch.float32, device=q.device)
+        L.check(lib.hpfg_attn_keys_bwd(L.ptr(q), L.ptr(kv), L.ptr(out), L.ptr(lse), L.ptr(do), L.ptr(dq), L.ptr(dkv), L.ptr(scratch), B, N, M, h, d,
+                                       ctx.scale, ctx.math, _st(q)), "attn_keys_bwd")
+        return dq, dkv, None, None
+
+
+def attention_keys(q: torch.Tensor, kv: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
+    """``attention`` for 1 .. MAX_KEYS_LONG keys (SegFormer above 256 x 256: a MiT stage has H/32 * W/32 keys).  Same layouts; for at
+    most MAX_KEYS keys the forward gives the bits of ``attention`` in the default math mode."""
+    C_ = q.shape[-1]
+    if C_ % heads or C_ // heads not in HEAD_DIMS:
+        raise ValueError(f"attention_keys: head dim {C_}/{heads} is not built; the HIP attention kernels exist for head dims {HEAD_DIMS}")
+    if kv.shape[-1] != 2 * C_ or not 1 <= kv.shape[1] <= MAX_KEYS_LONG:
+        raise ValueError(f"attention_keys: kv {tuple(kv.shape)} must be [B, 1 <= M <= {MAX_KEYS_LONG}, {2 * C_}] for q {tuple(q.shape)}: "
+                         f"the attention kernels take at most {MAX_KEYS_LONG} keys")
+    return _AttentionKeys.apply(q, kv, heads, scale)
+
+
+def attention_for(n_keys: int):
+    """The attention op the SegFormer branch uses for ``n_keys`` keys -- a function of the key count alone: ``attention`` up to MAX_KEYS
+    (every result at or below 256 x 256 keeps its bits), ``attention_keys`` above."""
+    return attention if n_keys <= MAX_KEYS else attention_keys
+
+
 class _DWGelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 135
+#define HPFG_VERSION 136
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -511,6 +511,25 @@ int hpfg_attn_mfma_fwd_hd(const float* q, const float* kv, float* out, int B, in
 int hpfg_attn_mfma_bwd_hd(const float* q, const float* kv, const float* dout, float* dq, float* dkv, float* scratch, int B, int N, int M, int heads,
                           int head_dim, float scale, void* stream);
 long hpfg_attn_mfma_scratch_floats(int B, int N, int heads, int head_dim);
+
+/* ---- attention core over 1 .. 256 keys (csrc/attn_keys.hip; reference model/segformer.py:92-128, whose Attention.forward has no key limit) -- */
+/* The most keys the entry points below take: 256 = the (512 / 32)^2 keys of a MiT stage at 512 x 512 (reference model/segformer.py:92-128). */
+int hpfg_attn_keys_max(void);
+/* Forward (reference model/segformer.py:92-128 after the q / kv projections): out = softmax(scale * q k^T) v per (image, head) as
+ * hpfg_attn_mfma_fwd_hd / hpfg_attn_fwd_hd, for 1 <= M <= hpfg_attn_keys_max() keys walked in blocks of 64; head_dim 32 or 64;
+ * math = HPFG_MATH_BF16X3 (split-bf16 MFMA products; for M <= 64 bit-identical to hpfg_attn_mfma_fwd_hd) or HPFG_MATH_F32 (exact fp32).
+ * lse [B,heads,N] receives the row log-sum-exp of the scaled scores (what the backward needs); it may be null (inference).  Returns -1 and
+ * sets hpfg_last_error on a bad shape, head dim, math mode or a null q / kv / out. */
+int hpfg_attn_keys_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int M, int heads, int head_dim, float scale, int math,
+                       void* stream);
+/* Backward of the above (reference model/segformer.py:92-128 under autograd) from the saved out and lse: dq like q, dkv like kv.
+ * delta = rowsum(dout . out), P = exp(S - lse), dS = P (dout V^T - delta); dK / dV partials per (query block, key block) are summed in a
+ * fixed order (no atomics: bit-identical from run to run).  scratch: hpfg_attn_keys_scratch_floats(...) floats.  No pointer may be null. */
+int hpfg_attn_keys_bwd(const float* q, const float* kv, const float* out, const float* lse, const float* dout, float* dq, float* dkv, float* scratch,
+                       int B, int N, int M, int heads, int head_dim, float scale, int math, void* stream);
+/* Floats of the backward's scratch for these arguments (reference model/segformer.py:92-128 needs none: autograd keeps the [B,heads,N,M]
+ * probabilities instead); -1 with hpfg_last_error set when hpfg_attn_keys_bwd would refuse them. */
+long hpfg_attn_keys_scratch_floats(int B, int N, int M, int heads, int head_dim, int math);
 
 /* ---- projection necks + Dense_Loss (UNet_Plus; reference model/unet.py:120-152, utils/loss/dense_loss.py:17-40) ------------------------ */
 /* C[m,n] = act(sum_k A(m,k) B(k,n) + bias[n]) in exact fp32 on the matrix cores; A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn], C row-major
