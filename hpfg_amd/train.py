@@ -1011,11 +1011,23 @@ def _sup_of(row, o=0):
     return 0.5 * (row[o + 1] + row[o + 2])
 
 
+def eval_hd95_route(args):
+    """The ``with_hd95`` argument of the evaluation for the config key ``eval_hd95``: absent or false -> False (HD95 logged as 0.0),
+    "host" -> True (scipy distance transforms), "device" -> "device" (hpfg_amd.val.hd95_device)."""
+    v = getattr(args, "eval_hd95", None)
+    if v is None or v is False:
+        return False
+    if isinstance(v, str) and v in ("host", "device"):
+        return True if v == "host" else "device"
+    raise ValueError(f"eval_hd95: {v!r} (absent / false, \"host\" or \"device\")")
+
+
 class _Best:
     """Periodic evaluation + best-Dice checkpoint of one network (main.py:224-279, 2017_03...py:116-152, sup_ACDC.py:97-116)."""
 
     def __init__(self, args, key, path_attr=None, path_fmt=None):
         self.args, self.key, self.best = args, key, 0.0
+        self.with_hd95 = eval_hd95_route(args)          # a bad value stops the loop before its first iteration, not at the first evaluation
         self.path_attr, self.path_fmt = path_attr, path_fmt
 
     def path(self):
@@ -1026,7 +1038,7 @@ class _Best:
     def __call__(self, model, optimizer, lr_scheduler, test_loader, cur_itrs, name="test"):
         from .val import test_acdc, test_synapse
         test = test_synapse if getattr(self.args, "datasets", None) in ("synapse", "sup_synapse") else test_acdc      # Synapse volumes: cubic-spline resize (val.py:196)
-        dice, hd95 = test(model=model, test_loader=test_loader, args=self.args, cur_itrs=cur_itrs, name=name)
+        dice, hd95 = test(model=model, test_loader=test_loader, args=self.args, cur_itrs=cur_itrs, name=name, with_hd95=self.with_hd95)
         logger = getattr(self.args, "logger", None)
         if logger is not None:
             logger.info("{}_dice: {:.4f} {}_hd95: {:.4f}".format(self.key, dice, self.key, hd95))

@@ -6,8 +6,9 @@ medpy's binary Dice ``2 n(A&B) / (n(A) + n(B))`` -- but without the per-slice ho
 becomes ONE device gather through an index map that scipy itself produces for the (shape, patch) pair (so the mapping is scipy's
 by construction), all slices go through the HIP engine in fixed-size batches, arg-max and the class-confusion counts are HIP
 kernels, and only C*C integers per volume cross to the host.
-HD95 (medpy ``hd95``, CPU distance transforms; out of scope of the hot path) is reported as 0.0 unless
-``with_hd95=True``, which runs the scipy restatement below on the host.
+HD95 (medpy ``hd95``) is reported as 0.0 unless asked for: ``with_hd95=True`` runs the scipy restatement below on the host (distance
+transforms of the whole volume, per class and direction), ``with_hd95="device"`` runs ``hd95_device``: surface extraction and an exact
+integer nearest-surface search in HIP (csrc/surface.hip), one sort, and two integers per class back to the host.
 
 ``test_synapse`` / ``test_single_volume_synapse`` (val.py:196-265) are the same machinery behind the other resize of the reference: every
 Synapse slice goes to ``patch_size`` with ``zoom(order=3)``, a cubic B-spline.  ``resize_cubic`` does that for a whole volume on the device
@@ -202,37 +203,129 @@ def hd95_host(pred: np.ndarray, gt: np.ndarray) -> float:
     return float(np.percentile(np.hstack((surf_dist(pred, gt), surf_dist(gt, pred))), 95))
 
 
-def test_single_volume(image, label, net, classes, patch_size=(256, 256), with_hd95: bool = False, _pred_out: list = None):
-    """Reference signature (val.py:268).  image, label: [1,S,h,w].  Returns [(dice, hd95)] for classes 1..classes-1.
+def hd95_order_stats(n: int) -> Tuple[int, int, float]:
+    """(k, k1, t): np.percentile(v, 95) of n values with numpy's default linear interpolation is lerp(sorted v[k], sorted v[k1], t) --
+    numpy's own virtual index n q + (alpha + q (1 - alpha - beta)) - 1 with q = 95 / 100, alpha = beta = 1, its floor and its fraction."""
+    q = 95 / 100
+    vi = n * q + (1.0 + q * (1.0 - 1.0 - 1.0)) - 1.0
+    if vi >= n - 1:
+        return n - 1, n - 1, 0.0
+    if vi < 0.0:
+        return 0, 0, 0.0
+    k = int(np.floor(vi))
+    return k, k + 1, float(vi - k)
+
+
+def hd95_finish(lo2: int, hi2: int, t: float) -> float:
+    """The 95th percentile from its two order statistics, given as the integer squared distances the device found: fp64 square roots, then
+    numpy's interpolation rule (a + (b - a) t, and b - (b - a)(1 - t) for t >= 0.5).  Pure host arithmetic."""
+    a, b = float(np.sqrt(np.float64(lo2))), float(np.sqrt(np.float64(hi2)))
+    d = b - a
+    return b - d * (1.0 - t) if t >= 0.5 else a + d * t
+
+
+_HD95_EMPTY_GT = "The second supplied array does not contain any binary object."      # medpy's text (hd95_host raises the same)
+
+
+def hd95_device(pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim: int = None) -> np.ndarray:
+    """HD95 of every foreground class (float64 [classes - 1]) of two uint8 label tensors on the device, [S,h,w] (ndim 3) or [h,w] (ndim 2; a
+    [1,h,w] tensor with ndim=2 is that slice): medpy hd95(pred == c, gt == c) with unit spacing, by hpfg_surface_counts / hpfg_surface_distances
+    (include/hpfg_hip.h) on the current stream.  The reference's rule per class (val.py:376-387): 0.0 if the class is never predicted; predicted
+    but absent from ``gt`` raises medpy's RuntimeError, decided from the surface counts before anything is searched.  Two transfers to the host:
+    the counts, and two order statistics per class.  No CPU fallback."""
+    if not (pred.is_cuda and gt.is_cuda and pred.dtype == torch.uint8 and gt.dtype == torch.uint8 and pred.shape == gt.shape):
+        raise ValueError("hd95_device takes two uint8 label tensors of one shape on the device (no CPU fallback)")
+    ndim = pred.dim() if ndim is None else int(ndim)
+    if pred.dim() not in (2, 3) or ndim not in (2, 3) or (pred.dim() == 2 and ndim != 2):
+        raise ValueError(f"hd95_device: a {pred.dim()}-D tensor with ndim={ndim} ([S,h,w] with ndim 3, [h,w] or [1,h,w] with ndim 2)")
+    s, h, w = (1,) + tuple(pred.shape) if pred.dim() == 2 else tuple(pred.shape)
+    lib = L.load()
+    p8, g8 = pred.contiguous(), gt.contiguous()
+    stream = torch.cuda.current_stream(pred.device).cuda_stream
+    counts_dev = torch.empty(L.SURFACE_SEGS, dtype=torch.int32, device=pred.device)
+    L.check(lib.hpfg_surface_counts(L.ptr(p8), L.ptr(g8), s, h, w, classes, ndim, L.ptr(counts_dev), stream), "surface_counts")
+    keep = counts_dev.cpu().numpy().astype(np.uint32)
+    out = np.zeros(classes - 1, dtype=np.float64)
+    for c in range(1, classes):
+        n_pred, n_gt = int(keep[2 * c - 2]), int(keep[2 * c - 1])          # a mask is empty exactly when its surface is
+        if n_pred == 0:
+            keep[2 * c - 2:2 * c] = 0
+        elif n_gt == 0:
+            raise RuntimeError(_HD95_EMPTY_GT)
+    total = int(keep.sum(dtype=np.int64))
+    if total == 0:
+        return out
+    need = lib.hpfg_surface_workspace_bytes(classes, total)
+    if need < 0:
+        raise ValueError(f"hd95_device: {total} surface points (below 2^31)")
+    ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+    L.check(lib.hpfg_surface_distances(L.ptr(p8), L.ptr(g8), s, h, w, classes, ndim, keep.ctypes.data_as(C.c_void_p), L.ptr(ws), need, stream),
+            "surface_distances")
+    keys = torch.sort(ws[256:256 + 4 * total].view(torch.int32)).values          # by (class, d^2): every class' two segments are adjacent
+    live, where, frac = [], [], []
+    base = 0
+    for c in range(1, classes):
+        n = int(keep[2 * c - 2]) + int(keep[2 * c - 1])
+        if n:
+            k, k1, t = hd95_order_stats(n)
+            live.append(c)
+            where += [base + k, base + k1]
+            frac.append(t)
+        base += n
+    got = (keys.index_select(0, torch.tensor(where, dtype=torch.int64).to(pred.device)).cpu().numpy().astype(np.int64) & 0x0FFFFFFF).reshape(-1, 2)
+    for c, (lo2, hi2), t in zip(live, got, frac):
+        out[c - 1] = hd95_finish(int(lo2), int(hi2), t)
+    return out
+
+
+def _hd95_route(with_hd95):
+    """False: none (0.0), True: ``hd95_host``, "device": ``hd95_device``."""
+    if isinstance(with_hd95, (bool, np.bool_)):
+        return bool(with_hd95)
+    if isinstance(with_hd95, str) and with_hd95 == "device":
+        return with_hd95
+    raise ValueError(f"with_hd95={with_hd95!r}: False (0.0), True (host) or \"device\"")
+
+
+def _volume_metrics(pred, lab, classes, with_hd95, ndim):
+    """[(dice, hd95)] for classes 1..classes-1 of a predicted and a true label tensor on the device (val.py:376-387 per class)."""
+    route = _hd95_route(with_hd95)
+    lab8 = lab.to(torch.uint8)
+    cm = confusion_counts(pred, lab8, classes)
+    hd = np.zeros(classes - 1)
+    if route == "device":
+        hd = hd95_device(pred, lab8, classes, ndim)
+    elif route:
+        pred_h, lab_h = pred.cpu().numpy(), lab.cpu().numpy()
+        hd = [hd95_host(pred_h == c, lab_h == c) if cm[:, c].sum() > 0 else 0.0 for c in range(1, classes)]
+    return [(dice_from_counts(cm, c), float(hd[c - 1])) for c in range(1, classes)]
+
+
+def test_single_volume(image, label, net, classes, patch_size=(256, 256), with_hd95=False, _pred_out: list = None):
+    """Reference signature (val.py:268).  image, label: [1,S,h,w].  Returns [(dice, hd95)] for classes 1..classes-1; hd95 is 0.0 with
+    ``with_hd95=False``, ``hd95_host`` with True and ``hd95_device`` with "device".
     _pred_out: optional list that receives the predicted label volume (uint8 [S,h,w], device) -- test_acdc's TensorBoard image hook."""
+    _hd95_route(with_hd95)
     dev = next(net.parameters()).device
     img = image.squeeze(0)
     lab = label.squeeze(0).to(dev)
     pred = predict_volume(img, net, patch_size)
     if _pred_out is not None:
         _pred_out.append(pred)
-    cm = confusion_counts(pred, lab.to(torch.uint8), classes)
-    out = []
-    pred_h = lab_h = None
-    for c in range(1, classes):
-        d = dice_from_counts(cm, c)
-        hd = 0.0
-        if with_hd95 and cm[:, c].sum() > 0:
-            if pred_h is None:
-                pred_h, lab_h = pred.cpu().numpy(), lab.cpu().numpy()
-            hd = hd95_host(pred_h == c, lab_h == c)
-        out.append((d, hd))
-    return out
+    return _volume_metrics(pred, lab, classes, with_hd95, 3)
 
 
 test_single_volume.__test__ = False      # reference name, not a pytest case
 
 
-def test_single_volume_synapse(image, label, net, classes, patch_size=(256, 256), test_save_path=None, case=None, z_spacing=1, _pred_out: list = None):
+def test_single_volume_synapse(image, label, net, classes, patch_size=(256, 256), test_save_path=None, case=None, z_spacing=1, _pred_out: list = None,
+                               with_hd95=False):
     """Reference signature (val.py:235).  image, label: [1,S,h,w], or [1,h,w] for the reference's 2-D branch (one slice, forwarded at its
     own size).  Every slice whose size differs from ``patch_size`` is resized with the cubic spline (``resize_cubic`` = zoom(order=3),
     val.py:243), forwarded, arg-maxed and resized back with order 0 (val.py:251).  Returns [(dice, hd95)] for classes 1..classes-1 with
-    hd95 = 0.0 as in ``test_single_volume``; ``test_save_path`` / ``case`` / ``z_spacing`` are unused there as well."""
+    hd95 chosen by ``with_hd95`` as in ``test_single_volume`` (the 2-D branch measures in the plane: ndim 2); ``test_save_path`` / ``case`` /
+    ``z_spacing`` are unused in the reference as well (medpy is called without voxelspacing)."""
+    _hd95_route(with_hd95)
     dev = next(net.parameters()).device
     img, lab = image.squeeze(0), label.squeeze(0).to(dev)
     if img.dim() == 2:
@@ -241,8 +334,7 @@ def test_single_volume_synapse(image, label, net, classes, patch_size=(256, 256)
         pred = predict_volume(img, net, patch_size, order=3)
     if _pred_out is not None:
         _pred_out.append(pred if pred.dim() == 3 else pred.unsqueeze(0))
-    cm = confusion_counts(pred, lab.to(torch.uint8), classes)
-    return [(dice_from_counts(cm, c), 0.0) for c in range(1, classes)]
+    return _volume_metrics(pred, lab, classes, with_hd95, pred.dim())
 
 
 test_single_volume_synapse.__test__ = False
@@ -273,7 +365,7 @@ def _test_volumes(single_volume, test_loader, args, cur_itrs, name):
     return float(np.mean(metric_list, axis=0)[0]), float(np.mean(metric_list, axis=0)[1])
 
 
-def test_acdc(model, test_loader, args, cur_itrs=0, name="test", with_hd95: bool = False):
+def test_acdc(model, test_loader, args, cur_itrs=0, name="test", with_hd95=False):
     """Reference signature (val.py:154): mean foreground Dice and mean HD95 over the volumes of ``test_loader`` (bs=1 volumes
     ``(image [1,S,h,w], label [1,S,h,w])``).  With ``args.writer`` (anything with TensorBoard's ``add_image``) the first volume's first slice
     is logged the way main.py:309-325 does: ``<name>/Image`` (the slice resized to ``test_crop_size``, [1,H,W]), ``<name>/label_pred`` and
@@ -286,12 +378,12 @@ def test_acdc(model, test_loader, args, cur_itrs=0, name="test", with_hd95: bool
 test_acdc.__test__ = False
 
 
-def test_synapse(model, test_loader, args, cur_itrs=0, name="test"):
+def test_synapse(model, test_loader, args, cur_itrs=0, name="test", with_hd95=False):
     """Reference signature (val.py:196): ``test_acdc`` with ``test_single_volume_synapse`` per volume -- the slices reach the network through
     the cubic-spline resize.  The image hooks are those of ``test_acdc`` (the shown slice is resized with order 0 there too, val.py:215); the
     logged prediction is slice 0 of the scored volume prediction."""
     return _test_volumes(lambda image, label, keep: test_single_volume_synapse(image, label, model, classes=args.num_classes,
-                                                                               patch_size=args.test_crop_size, _pred_out=keep),
+                                                                               patch_size=args.test_crop_size, _pred_out=keep, with_hd95=with_hd95),
                          test_loader, args, cur_itrs, name)
 
 

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 136
+#define HPFG_VERSION 137
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -391,6 +391,29 @@ int hpfg_confusion_counts(const uint8_t* pred, const uint8_t* gt, long n, int C,
 int hpfg_resize_cubic(const float* src, int S, int h, int w, float* dst, int H, int W, const float* taps_y, const float* taps_x, void* scratch,
                       long scratch_bytes, void* stream);
 long hpfg_resize_cubic_scratch_bytes(int S, int h, int w, int H, int W);
+/* evaluation (val.py:376-387, medpy binary hd95 of pred == c against gt == c for every foreground class c = 1 .. C-1, no voxelspacing): the
+ * surface distances of a predicted and a true label volume, uint8 [S][h][w] contiguous; labels >= C belong to no mask.  medpy's operations
+ * restated: the surface of a mask is mask ^ scipy.ndimage.binary_erosion(mask, generate_binary_structure(ndim, 1)) (border_value 0): the
+ * mask voxels with one of their 2 * ndim face neighbours outside the mask or outside the volume (ndim 2: S = 1 and only the in-plane
+ * neighbours; ndim 3: the z neighbours count, so every voxel of an S = 1 volume is a surface voxel); the distance of a surface voxel is
+ * distance_transform_edt(~other surface) there: with unit spacing the square root of an integer d^2 = dz^2 + dy^2 + dx^2 < 2^28, which the
+ * device finds exactly by an exhaustive integer search.  Segment (c - 1) * 2 + side holds the surface voxels of class c, side 0 = pred, 1 = gt.
+ *   hpfg_surface_counts     counts[HPFG_SURFACE_SEGS] (device; zeroed by the call) = surface voxels per segment
+ *   hpfg_surface_distances  counts_host[HPFG_SURFACE_SEGS] (HOST memory): the points to keep per segment -- the counts above, or 0 for a
+ *       segment to skip (a class that needs no search; both of its segments); never more points are written than it says.  Offsets are the
+ *       running sum of counts_host.  workspace (device, 16-byte aligned, hpfg_surface_workspace_bytes(C, n), n = sum of counts_host):
+ *         bytes [0, 256)  cursors;  from 256: int32 keys[n];  from 256 + 4 n rounded up to 256: int32 points[n] (linear voxel indices).
+ *       keys[offset(seg) + i] = ((c - 1) << 28 | d^2) ^ 0x80000000 read as a signed integer, d^2 = squared distance from point i of the
+ *       segment to the nearest point of the same class' other side: one signed sort of keys[0, n) orders every class' 2 segments (which are
+ *       adjacent: medpy's hstack) by d^2, classes ascending, and d^2 = key & 0x0FFFFFFF.  A segment that is empty or whose partner is empty
+ *       launches nothing; its keys stay 0x7F7F7F7F.  Four launches and fills whatever C is.
+ * All three refuse (-1): a null pointer, ndim not 2 or 3, ndim 2 with S != 1, C outside 2 .. 16, an axis longer than 8192
+ * (3 * 8191^2 < 2^28), S * h * w >= 2^31; hpfg_surface_workspace_bytes: C outside 2 .. 16, n outside 0 .. 2^31 - 1. */
+#define HPFG_SURFACE_SEGS 32
+int hpfg_surface_counts(const uint8_t* pred, const uint8_t* gt, int S, int h, int w, int C, int ndim, unsigned int* counts, void* stream);
+int hpfg_surface_distances(const uint8_t* pred, const uint8_t* gt, int S, int h, int w, int C, int ndim, const unsigned int* counts_host,
+                           void* workspace, long workspace_bytes, void* stream);
+long hpfg_surface_workspace_bytes(int C, long n_points);
 /* Training-time slice augmentation on the device (datasets/utils.py:73-117 RandomGenerator.__call__: random_rot_flip | random_rotate,
  * then scipy zoom(order=0) to the network size, image and mask alike).  The host draws the random parameters in the reference's
  * order and supplies, per sample, the source slice, the rot90/flip or rotation parameters (rotation matrix and offset exactly
