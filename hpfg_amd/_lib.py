@@ -19,7 +19,7 @@ OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP = 0, 1, 2, 3    
 LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
 LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 137
+VERSION = 138
 RESIZE_TAPS = 36            # HPFG_RESIZE_TAPS: coefficients per output sample and axis of hpfg_resize_cubic's tap tables
 SURFACE_SEGS = 32           # HPFG_SURFACE_SEGS: surface-point segments of hpfg_surface_*, (class - 1) * 2 + side (0 = pred, 1 = gt)
 MATH_F32, MATH_BF16X3 = 0, 1
@@ -165,6 +165,7 @@ PROTOTYPES = {
     "hpfg_surface_counts": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "hpfg_surface_distances": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _l, _p]),
     "hpfg_surface_workspace_bytes": (_l, [_i, _l]),
+    "hpfg_surface_sums": (_i, [_p, _l, _i, _p, _p, _p]),
     "hpfg_box_masks": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "hpfg_augment_batch": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "hpfg_timestamp": (_i, [_p, _p]),

@@ -11,6 +11,7 @@
 //                                points (every lane reads the same 16-byte slot: a broadcast), integer d^2 = dz^2 + dy^2 + dx^2 from 24-bit
 //                                multiplies, minimum by integer atomicMin (order independent).  All classes and both directions are one
 //                                launch: a block looks its (segment, query block, target split) up in a table passed by value.
+//   surface_sums_kernel          the exact sum of sqrt(d^2) over every searched segment, for ASD (val.py:109-122): integer atomics only
 // A voxel of a mask is on its surface when one of its 2 * ndim face neighbours is outside the mask or outside the volume
 // (mask ^ binary_erosion(mask, generate_binary_structure(ndim, 1)), border_value = 0).
 #include "common.h"
@@ -123,6 +124,45 @@ __global__ __launch_bounds__(SURF_TILE) void surface_nearest_kernel(const int* _
   if (q < nq) atomicMin(&keys[(long)t.off[s] + q], (int)((((unsigned)(s >> 1) << 28) | best) ^ SURF_KEY_BIAS));
 }
 
+// ASD of the evaluation (val.py:109-122: medpy.metric.binary.asd = the mean of one direction's surface distances): the sum of sqrt(d^2) over
+// every segment's keys, exactly.  The order of the points inside a segment is arbitrary (the compaction's atomic cursor), so nothing that
+// rounds may be added up: x = sqrt((double)d^2) is 0 or in [1, 2^14), hence a multiple of 2^-52, and splits without loss into
+// hi = rint(x * 2^19) <= 2^33 and lo = (x - hi * 2^-19) * 2^52, an integer with |lo| <= 2^32.  Both are added with integer atomics (LDS per
+// workgroup, then one global atomic per workgroup and touched word): associative, so the totals are the same bits in any order, and
+// 2^31 - 1 points overflow neither word.  sum = hi * 2^-19 + lo * 2^-52; the host divides by the count in rational arithmetic.
+constexpr double SURF_SUM_HI = 524288.0;                    // 2^19
+constexpr double SURF_SUM_LO = 4503599627370496.0;          // 2^52
+
+struct SurfSumTable {
+  unsigned off[SEGS + 1];          // first key of every segment (running sum of the counts)
+  unsigned live;                   // bit s: segment s is summed (searched: neither it nor its partner is empty)
+};
+
+// grid: one thread per key.  sums[2 s] += hi, sums[2 s + 1] += lo (two's complement) over the keys of every live segment s.
+__global__ __launch_bounds__(256) void surface_sums_kernel(const int* __restrict__ keys, SurfSumTable t, unsigned long long* __restrict__ sums) {
+  __shared__ unsigned long long lsum[2 * SEGS];
+  const int tid = threadIdx.x;
+  if (tid < 2 * SEGS) lsum[tid] = 0;
+  __syncthreads();
+  const unsigned i = blockIdx.x * 256u + tid;          // (below 2^31 + 256)
+  if (i < t.off[SEGS]) {
+    int s = 0;          // off is non-decreasing: the segment of key i is the number of boundaries off[1 .. SEGS-1] at or below i
+#pragma unroll
+    for (int k = 1; k < SEGS; ++k) s += i >= t.off[k] ? 1 : 0;
+    if ((t.live >> s) & 1u) {
+#pragma clang fp contract(off)
+      const unsigned d2 = ((unsigned)keys[i] ^ SURF_KEY_BIAS) & 0x0FFFFFFFu;
+      const double x = sqrt((double)d2);
+      const double hi = rint(x * SURF_SUM_HI);
+      const double lo = (x - hi * (1.0 / SURF_SUM_HI)) * SURF_SUM_LO;
+      atomicAdd(&lsum[2 * s], (unsigned long long)hi);
+      atomicAdd(&lsum[2 * s + 1], (unsigned long long)(long long)lo);
+    }
+  }
+  __syncthreads();
+  if (tid < 2 * SEGS && lsum[tid]) atomicAdd(&sums[tid], lsum[tid]);
+}
+
 static int surface_dims_check(const char* who, int S, int h, int w, int C, int ndim) {
   HPFG_ARG_CHECK(ndim == 2 || ndim == 3, "%s: ndim %d (2 or 3)", who, ndim);
   HPFG_ARG_CHECK(C >= 2 && C <= 16, "%s: %d classes (2 .. 16)", who, C);
@@ -206,4 +246,27 @@ extern "C" int hpfg_surface_distances(const uint8_t* pred, const uint8_t* gt, in
   if (blocks > 0)
     hipLaunchKernelGGL(surface_nearest_kernel, dim3((unsigned)blocks), dim3(SURF_TILE), 0, (hipStream_t)stream, (const int*)points, keys, t, h, w);
   return hpfg_launch_status("surface_distances");
+}
+
+extern "C" int hpfg_surface_sums(const void* workspace, long workspace_bytes, int C, const unsigned int* counts_host, long long* sums, void* stream) {
+  HPFG_ARG_CHECK(workspace && counts_host && sums, "surface_sums: null pointer");
+  HPFG_ARG_CHECK(C >= 2 && C <= 16, "surface_sums: %d classes (2 .. 16)", C);
+  const long total = surface_total(counts_host, C);
+  HPFG_ARG_CHECK(total >= 0, "surface_sums: counts beyond the %d segments of %d classes, or 2^31 points or more", 2 * (C - 1), C);
+  HPFG_ARG_CHECK(workspace_bytes >= hpfg_surface_workspace_bytes(C, total), "surface_sums: workspace of %ld bytes, %ld needed", workspace_bytes,
+                 hpfg_surface_workspace_bytes(C, total));
+  HPFG_ARG_CHECK((uintptr_t)workspace % 16 == 0 && (uintptr_t)sums % 8 == 0, "surface_sums: misaligned workspace or sums");
+  SurfSumTable t;
+  t.off[0] = 0;
+  t.live = 0;
+  for (int s = 0; s < SEGS; ++s) {
+    t.off[s + 1] = t.off[s] + counts_host[s];
+    if (s < 2 * (C - 1) && counts_host[s] > 0 && counts_host[s ^ 1] > 0) t.live |= 1u << s;          // the segments hpfg_surface_distances searched
+  }
+  hipError_t e = hipMemsetAsync(sums, 0, 2 * SEGS * sizeof(long long), (hipStream_t)stream);
+  HPFG_ARG_CHECK(e == hipSuccess, "surface_sums: %s", hipGetErrorString(e));
+  if (t.live)
+    hipLaunchKernelGGL(surface_sums_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const int*)((const char*)workspace + 256), t, (unsigned long long*)sums);
+  return hpfg_launch_status("surface_sums");
 }

@@ -82,6 +82,15 @@ def _size(args):
     return (s, s) if isinstance(s, int) else (s[0], s[1])
 
 
+def _test_loader(args, in_ch: int, ncls: int, seed: int):
+    """The test split: bs=1 volumes, or -- with the config key ``synthetic_test_images: N`` -- N single images in batches of ``batch_size``
+    (image [B,in_ch,H,W], label [B,H,W]; the last batch may be short), the contract of the reference's 2-D test sets (val.py:86-151)."""
+    n_img = args.get("synthetic_test_images", None)
+    if n_img is not None:
+        return DataLoader(SyntheticSlices(int(n_img), _size(args), in_ch, ncls, seed), batch_size=args.batch_size, shuffle=False)
+    return DataLoader(SyntheticVolumes(int(args.get("synthetic_test_volumes", 2)), 8, _size(args), ncls, seed), batch_size=1, shuffle=False)
+
+
 def get_ssl_synthetic_loader(args, rank: int = 0):
     n_lab = int(args.get("synthetic_labeled", 256))
     n_unl = int(args.get("synthetic_unlabeled", 1024))
@@ -92,20 +101,18 @@ def get_ssl_synthetic_loader(args, rank: int = 0):
     seed = 1234 + rank
     lab = SyntheticSlices(n_lab, _size(args), in_ch, ncls, seed)
     unl = SyntheticSlices(n_unl, _size(args), in_ch, ncls, seed + 100003)
-    test = SyntheticVolumes(int(args.get("synthetic_test_volumes", 2)), 8, _size(args), ncls, seed + 200003)
     g = torch.Generator().manual_seed(seed)
     label_loader = DataLoader(lab, batch_size=args.batch_size, shuffle=True, drop_last=True, num_workers=0, generator=g)
     unlabel_loader = DataLoader(unl, batch_size=args.unlabel_batch_size, shuffle=True, drop_last=True, num_workers=0, generator=g)
-    test_loader = DataLoader(test, batch_size=1, shuffle=False)
-    return label_loader, unlabel_loader, test_loader
+    return label_loader, unlabel_loader, _test_loader(args, in_ch, ncls, seed + 200003)
 
 
 def get_synthetic_loader(args, rank: int = 0):
     n = int(args.get("synthetic_labeled", 8))
     ncls = int(args.num_classes)
     seed = 1234 + rank
-    ds = SyntheticSlices(n, _size(args), int(args.get("in_channels", 1)), ncls, seed)
-    test = SyntheticVolumes(int(args.get("synthetic_test_volumes", 2)), 8, _size(args), ncls, seed + 200003)
+    in_ch = int(args.get("in_channels", 1))
+    ds = SyntheticSlices(n, _size(args), in_ch, ncls, seed)
     g = torch.Generator().manual_seed(seed)
     return (DataLoader(ds, batch_size=args.batch_size, shuffle=True, drop_last=True, num_workers=0, generator=g),
-            DataLoader(test, batch_size=1, shuffle=False))
+            _test_loader(args, in_ch, ncls, seed + 200003))

@@ -1022,12 +1022,24 @@ def eval_hd95_route(args):
     raise ValueError(f"eval_hd95: {v!r} (absent / false, \"host\" or \"device\")")
 
 
+def eval_images_route(args):
+    """The config key ``eval_images``: absent or false -> None (volumes: ``test_acdc`` / ``test_synapse``), "lidc" / "isic" -> that name (image batches:
+    ``hpfg_amd.val.test_lidc`` / ``test_isic``)."""
+    v = getattr(args, "eval_images", None)
+    if v is None or v is False:
+        return None
+    if isinstance(v, str) and v in ("lidc", "isic"):
+        return v
+    raise ValueError(f"eval_images: {v!r} (absent / false, \"lidc\" or \"isic\")")
+
+
 class _Best:
     """Periodic evaluation + best-Dice checkpoint of one network (main.py:224-279, 2017_03...py:116-152, sup_ACDC.py:97-116)."""
 
     def __init__(self, args, key, path_attr=None, path_fmt=None):
         self.args, self.key, self.best = args, key, 0.0
         self.with_hd95 = eval_hd95_route(args)          # a bad value stops the loop before its first iteration, not at the first evaluation
+        self.images = eval_images_route(args)
         self.path_attr, self.path_fmt = path_attr, path_fmt
 
     def path(self):
@@ -1036,12 +1048,17 @@ class _Best:
         return getattr(self.args, self.path_attr, None) if self.path_attr else None
 
     def __call__(self, model, optimizer, lr_scheduler, test_loader, cur_itrs, name="test"):
-        from .val import test_acdc, test_synapse
+        from .val import test_acdc, test_isic, test_lidc, test_synapse
         test = test_synapse if getattr(self.args, "datasets", None) in ("synapse", "sup_synapse") else test_acdc      # Synapse volumes: cubic-spline resize (val.py:196)
-        dice, hd95 = test(model=model, test_loader=test_loader, args=self.args, cur_itrs=cur_itrs, name=name, with_hd95=self.with_hd95)
+        if self.images is not None:          # 2-D image test sets (val.py:86, 125)
+            test = test_isic if self.images == "isic" else test_lidc
+        dice, hd95, *more = test(model=model, test_loader=test_loader, args=self.args, cur_itrs=cur_itrs, name=name, with_hd95=self.with_hd95)
         logger = getattr(self.args, "logger", None)
         if logger is not None:
-            logger.info("{}_dice: {:.4f} {}_hd95: {:.4f}".format(self.key, dice, self.key, hd95))
+            line = "{}_dice: {:.4f} {}_hd95: {:.4f}".format(self.key, dice, self.key, hd95)
+            if more:
+                line += " {}_jac: {:.4f} {}_asd: {:.4f}".format(self.key, more[0], self.key, more[1])
+            logger.info(line)
         if dice > self.best:
             self.best = dice
             path = self.path()

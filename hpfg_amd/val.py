@@ -13,6 +13,11 @@ integer nearest-surface search in HIP (csrc/surface.hip), one sort, and two inte
 ``test_synapse`` / ``test_single_volume_synapse`` (val.py:196-265) are the same machinery behind the other resize of the reference: every
 Synapse slice goes to ``patch_size`` with ``zoom(order=3)``, a cubic B-spline.  ``resize_cubic`` does that for a whole volume on the device
 (hpfg_resize_cubic, csrc/resize.hip) from per-axis tap tables built here on the host in fp64; the resize back stays order 0.
+
+``test_lidc`` / ``test_isic`` (val.py:86-151) score 2-D image test sets: batches ``[B,Cin,H,W]`` at network size, no resize, class 1 only, every
+batch one ``[B,H,W]`` array for the metrics.  Dice and Jaccard come from the confusion counts; HD95 and medpy's average surface distance (ASD)
+by the same ``with_hd95`` routes -- on the device one surface pass serves both (``surface_metrics_device``): hpfg_surface_sums adds the
+distances of a segment exactly in integers, so the mean does not depend on the order the surface points were found in.
 """
 from __future__ import annotations
 
@@ -183,6 +188,14 @@ def dice_from_counts(cm: np.ndarray, cls: int) -> float:
     return 2.0 * inter / float(n_pred + n_gt)
 
 
+def jaccard_from_counts(cm: np.ndarray, cls: int) -> float:
+    """medpy jc, intersection over union, from the confusion counts; 0 if the class is never predicted (val.py:109-122)."""
+    n_pred, n_gt, inter = int(cm[:, cls].sum()), int(cm[cls, :].sum()), int(cm[cls, cls])
+    if n_pred == 0:
+        return 0.0
+    return inter / float(n_pred + n_gt - inter)
+
+
 def hd95_host(pred: np.ndarray, gt: np.ndarray) -> float:
     """medpy.metric.binary.hd95 restated with scipy (voxel spacing 1, connectivity 1): 95th percentile of the symmetric surface
     distances.  Host only; raises like medpy when one of the objects is empty."""
@@ -227,17 +240,45 @@ def hd95_finish(lo2: int, hi2: int, t: float) -> float:
 _HD95_EMPTY_GT = "The second supplied array does not contain any binary object."      # medpy's text (hd95_host raises the same)
 
 
-def hd95_device(pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim: int = None) -> np.ndarray:
-    """HD95 of every foreground class (float64 [classes - 1]) of two uint8 label tensors on the device, [S,h,w] (ndim 3) or [h,w] (ndim 2; a
-    [1,h,w] tensor with ndim=2 is that slice): medpy hd95(pred == c, gt == c) with unit spacing, by hpfg_surface_counts / hpfg_surface_distances
-    (include/hpfg_hip.h) on the current stream.  The reference's rule per class (val.py:376-387): 0.0 if the class is never predicted; predicted
-    but absent from ``gt`` raises medpy's RuntimeError, decided from the surface counts before anything is searched.  Two transfers to the host:
-    the counts, and two order statistics per class.  No CPU fallback."""
+def asd_host(pred: np.ndarray, gt: np.ndarray) -> float:
+    """medpy.metric.binary.asd(result=pred, reference=gt) restated with scipy (voxel spacing 1, connectivity 1): the mean distance from the
+    surface voxels of ``pred`` to the surface of ``gt`` -- one direction only.  Host only; raises like medpy when one of the objects is empty."""
+    from scipy.ndimage import binary_erosion, distance_transform_edt, generate_binary_structure
+    a, b = np.atleast_1d(np.asarray(pred).astype(bool)), np.atleast_1d(np.asarray(gt).astype(bool))
+    if not a.any():
+        raise RuntimeError("The first supplied array does not contain any binary object.")
+    if not b.any():
+        raise RuntimeError(_HD95_EMPTY_GT)
+    fp = generate_binary_structure(a.ndim, 1)
+    ab = a ^ binary_erosion(a, structure=fp, iterations=1)
+    bb = b ^ binary_erosion(b, structure=fp, iterations=1)
+    return float(distance_transform_edt(~bb)[ab].mean())
+
+
+def asd_limbs(d2) -> Tuple[np.ndarray, np.ndarray]:
+    """The two integers hpfg_surface_sums adds per point (include/hpfg_hip.h), for integer squared distances ``d2`` below 2^28: with
+    x = sqrt(d2) in fp64, hi = rint(x * 2^19) and lo = (x - hi * 2^-19) * 2^52, so that x == hi * 2^-19 + lo * 2^-52 exactly.  Host
+    restatement of the device arithmetic (int64 arrays)."""
+    x = np.sqrt(np.asarray(d2, dtype=np.float64))
+    hi = np.rint(x * 2.0 ** 19)
+    lo = (x - hi * 2.0 ** -19) * 2.0 ** 52
+    return hi.astype(np.int64), lo.astype(np.int64)
+
+
+def asd_finish(hi: int, lo: int, n: int) -> float:
+    """The mean of n distances from their exact sum hi * 2^-19 + lo * 2^-52 (the two integer words of hpfg_surface_sums): rational arithmetic,
+    rounded once to fp64.  Pure host arithmetic."""
+    from fractions import Fraction
+    return float(Fraction((int(hi) << 33) + int(lo), int(n) << 52))
+
+
+def _surface_pass(who: str, pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim, with_asd: bool):
+    """The body of ``hd95_device`` and ``surface_metrics_device``: (hd95, asd), float64 [classes - 1] each (asd is None unless asked for)."""
     if not (pred.is_cuda and gt.is_cuda and pred.dtype == torch.uint8 and gt.dtype == torch.uint8 and pred.shape == gt.shape):
-        raise ValueError("hd95_device takes two uint8 label tensors of one shape on the device (no CPU fallback)")
+        raise ValueError(f"{who} takes two uint8 label tensors of one shape on the device (no CPU fallback)")
     ndim = pred.dim() if ndim is None else int(ndim)
     if pred.dim() not in (2, 3) or ndim not in (2, 3) or (pred.dim() == 2 and ndim != 2):
-        raise ValueError(f"hd95_device: a {pred.dim()}-D tensor with ndim={ndim} ([S,h,w] with ndim 3, [h,w] or [1,h,w] with ndim 2)")
+        raise ValueError(f"{who}: a {pred.dim()}-D tensor with ndim={ndim} ([S,h,w] with ndim 3, [h,w] or [1,h,w] with ndim 2)")
     s, h, w = (1,) + tuple(pred.shape) if pred.dim() == 2 else tuple(pred.shape)
     lib = L.load()
     p8, g8 = pred.contiguous(), gt.contiguous()
@@ -246,6 +287,7 @@ def hd95_device(pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim: int = 
     L.check(lib.hpfg_surface_counts(L.ptr(p8), L.ptr(g8), s, h, w, classes, ndim, L.ptr(counts_dev), stream), "surface_counts")
     keep = counts_dev.cpu().numpy().astype(np.uint32)
     out = np.zeros(classes - 1, dtype=np.float64)
+    asd = np.zeros(classes - 1, dtype=np.float64) if with_asd else None
     for c in range(1, classes):
         n_pred, n_gt = int(keep[2 * c - 2]), int(keep[2 * c - 1])          # a mask is empty exactly when its surface is
         if n_pred == 0:
@@ -254,13 +296,16 @@ def hd95_device(pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim: int = 
             raise RuntimeError(_HD95_EMPTY_GT)
     total = int(keep.sum(dtype=np.int64))
     if total == 0:
-        return out
+        return out, asd
     need = lib.hpfg_surface_workspace_bytes(classes, total)
     if need < 0:
-        raise ValueError(f"hd95_device: {total} surface points (below 2^31)")
+        raise ValueError(f"{who}: {total} surface points (below 2^31)")
     ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
     L.check(lib.hpfg_surface_distances(L.ptr(p8), L.ptr(g8), s, h, w, classes, ndim, keep.ctypes.data_as(C.c_void_p), L.ptr(ws), need, stream),
             "surface_distances")
+    if with_asd:          # from the unsorted keys, which stay in the workspace: the sort below makes a copy
+        sums = torch.empty(2 * L.SURFACE_SEGS, dtype=torch.int64, device=pred.device)
+        L.check(lib.hpfg_surface_sums(L.ptr(ws), need, classes, keep.ctypes.data_as(C.c_void_p), L.ptr(sums), stream), "surface_sums")
     keys = torch.sort(ws[256:256 + 4 * total].view(torch.int32)).values          # by (class, d^2): every class' two segments are adjacent
     live, where, frac = [], [], []
     base = 0
@@ -275,7 +320,28 @@ def hd95_device(pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim: int = 
     got = (keys.index_select(0, torch.tensor(where, dtype=torch.int64).to(pred.device)).cpu().numpy().astype(np.int64) & 0x0FFFFFFF).reshape(-1, 2)
     for c, (lo2, hi2), t in zip(live, got, frac):
         out[c - 1] = hd95_finish(int(lo2), int(hi2), t)
-    return out
+    if with_asd:
+        words = sums.cpu().numpy().reshape(L.SURFACE_SEGS, 2)
+        for c in live:          # segment (c - 1) * 2: pred -> gt (medpy asd(result, reference))
+            asd[c - 1] = asd_finish(int(words[2 * c - 2, 0]) & (2 ** 64 - 1), int(words[2 * c - 2, 1]), int(keep[2 * c - 2]))
+    return out, asd
+
+
+def hd95_device(pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim: int = None) -> np.ndarray:
+    """HD95 of every foreground class (float64 [classes - 1]) of two uint8 label tensors on the device, [S,h,w] (ndim 3) or [h,w] (ndim 2; a
+    [1,h,w] tensor with ndim=2 is that slice): medpy hd95(pred == c, gt == c) with unit spacing, by hpfg_surface_counts / hpfg_surface_distances
+    (include/hpfg_hip.h) on the current stream.  The reference's rule per class (val.py:376-387): 0.0 if the class is never predicted; predicted
+    but absent from ``gt`` raises medpy's RuntimeError, decided from the surface counts before anything is searched.  Two transfers to the host:
+    the counts, and two order statistics per class.  No CPU fallback."""
+    return _surface_pass("hd95_device", pred, gt, classes, ndim, False)[0]
+
+
+def surface_metrics_device(pred: torch.Tensor, gt: torch.Tensor, classes: int, ndim: int = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(hd95, asd) of every foreground class, float64 [classes - 1] each: ``hd95_device`` (the same pass, the same bits) and medpy
+    asd(pred == c, gt == c) -- the mean distance from the surface of the prediction to the surface of ``gt`` -- from the same surface
+    distances, summed exactly by hpfg_surface_sums and divided on the host (``asd_finish``).  The rule per class and the RuntimeError are
+    those of ``hd95_device``: a class that is never predicted gives 0.0 for both.  One more transfer to the host: the 64 sum words."""
+    return _surface_pass("surface_metrics_device", pred, gt, classes, ndim, True)
 
 
 def _hd95_route(with_hd95):
@@ -388,3 +454,91 @@ def test_synapse(model, test_loader, args, cur_itrs=0, name="test", with_hd95=Fa
 
 
 test_synapse.__test__ = False
+
+
+def predict_images(images: torch.Tensor, net) -> torch.Tensor:
+    """images [B,Cin,H,W] (float, any device) -> predicted labels uint8 [B,H,W] on the model's device: the eval-mode forward and arg-max of
+    val.py:94,135 at the images' own size, in engine batches of ``EVAL_BATCH`` (the last one zero padded), as ``predict_volume`` runs its slices."""
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("hpfg_amd.val runs on the HIP library only (no CPU fallback)")
+    if images.dim() != 4:
+        raise ValueError(f"predict_images: a {images.dim()}-D tensor ([B,Cin,H,W])")
+    x = images.to(dev, torch.float32)
+    b = x.shape[0]
+    was_training = net.training
+    net.eval()
+    fwd = net.val if hasattr(net, "val") else net
+    preds: List[torch.Tensor] = []
+    with torch.no_grad():
+        for i in range(0, b, EVAL_BATCH):
+            chunk = x[i:i + EVAL_BATCH]
+            n = chunk.shape[0]
+            if n < EVAL_BATCH:
+                chunk = torch.cat([chunk, chunk.new_zeros(EVAL_BATCH - n, *chunk.shape[1:])], 0)
+            preds.append(argmax_labels(fwd(chunk.contiguous()))[:n])       # argmax(softmax(z)) == argmax(z)
+    net.train(was_training)
+    return torch.cat(preds, 0).contiguous()
+
+
+def _batch_metrics(pred: torch.Tensor, lab: torch.Tensor, with_hd95) -> Tuple[float, float, float, float]:
+    """(dice, hd95, jac, asd) of class 1 of one image batch scored as a whole, the reference's ``cal`` (val.py:109-122) on (pred == 1) against
+    (label == 1) as one [B,H,W] array: nothing predicted -> zeros; Dice and Jaccard from the device confusion counts; the two surface metrics
+    by the ``with_hd95`` route (0.0 / host / device), where a prediction against labels without the class raises medpy's RuntimeError."""
+    route = _hd95_route(with_hd95)
+    p1, g1 = (pred == 1).to(torch.uint8), (lab == 1).to(torch.uint8)
+    cm = confusion_counts(p1, g1, 2)
+    if cm[:, 1].sum() == 0:
+        return 0.0, 0.0, 0.0, 0.0
+    hd, asd = 0.0, 0.0
+    if route == "device":
+        hd, asd = (float(v[0]) for v in surface_metrics_device(p1, g1, 2, 3))
+    elif route:
+        ph, gh = p1.cpu().numpy() == 1, g1.cpu().numpy() == 1
+        hd, asd = hd95_host(ph, gh), asd_host(ph, gh)
+    return dice_from_counts(cm, 1), hd, jaccard_from_counts(cm, 1), asd
+
+
+def _side_by_side(img: np.ndarray) -> np.ndarray:
+    """[B,H,W,3] palette images of a batch -> one [H,B*W,3] image (a ``label_to_img`` that already returns one image passes through)."""
+    return np.concatenate(list(img), axis=1) if img.ndim == 4 else img
+
+
+def _test_images(model, test_loader, args, cur_itrs, name, with_hd95) -> np.ndarray:
+    """The body ``test_lidc`` and ``test_isic`` share (val.py:86-106, 125-151): [dice, hd95, jac, asd] of class 1, every batch of
+    ``test_loader`` (``(image [B,Cin,H,W], label [B,H,W])``) scored as a whole and weighted by its size, over ``len(test_loader.dataset)``."""
+    _hd95_route(with_hd95)
+    dev = next(model.parameters()).device
+    total = np.zeros(4, dtype=np.float64)
+    writer = getattr(args, "writer", None)
+    to_img = getattr(getattr(test_loader, "dataset", None), "label_to_img", None)
+    for i, (img, label_true) in enumerate(test_loader):
+        pred = predict_images(img, model)
+        lab = label_true.to(dev)
+        total += np.array(_batch_metrics(pred, lab, with_hd95), dtype=np.float64) * img.shape[0]
+        if i == 0 and writer is not None and hasattr(writer, "add_image") and to_img is not None:
+            writer.add_image("{}/label_pred".format(name), _side_by_side(to_img(pred.cpu().numpy())), cur_itrs, dataformats="HWC")
+            writer.add_image("{}/label_true".format(name), _side_by_side(to_img(label_true.cpu().numpy())), cur_itrs, dataformats="HWC")
+    return total / len(test_loader.dataset)
+
+
+def test_lidc(model, test_loader, args, cur_itrs=0, name="test", with_hd95=False):
+    """Reference signature (val.py:86) plus ``with_hd95``: (dice, hd95) of class 1 over a loader of image batches, each batch one [B,H,W]
+    array for the metrics (surfaces connect across the batch axis; a batch of one is a one-slice volume), whatever ``num_classes`` is.
+    With ``args.writer`` the first batch's ``<name>/label_pred`` and ``<name>/label_true`` palette images are logged; the reference's
+    ``make_grid`` picture of the input images (``<name>/Image``) is not."""
+    m = _test_images(model, test_loader, args, cur_itrs, name, with_hd95)
+    return float(m[0]), float(m[1])
+
+
+test_lidc.__test__ = False
+
+
+def test_isic(model, test_loader, args, cur_itrs=0, name="test", with_hd95=False):
+    """Reference signature (val.py:125) plus ``with_hd95``: ``test_lidc`` with medpy's Jaccard index and average surface distance,
+    (dice, hd95, jac, asd); ``with_hd95`` chooses the route of both surface metrics."""
+    m = _test_images(model, test_loader, args, cur_itrs, name, with_hd95)
+    return float(m[0]), float(m[1]), float(m[2]), float(m[3])
+
+
+test_isic.__test__ = False

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 137
+#define HPFG_VERSION 138
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -414,6 +414,16 @@ int hpfg_surface_counts(const uint8_t* pred, const uint8_t* gt, int S, int h, in
 int hpfg_surface_distances(const uint8_t* pred, const uint8_t* gt, int S, int h, int w, int C, int ndim, const unsigned int* counts_host,
                            void* workspace, long workspace_bytes, void* stream);
 long hpfg_surface_workspace_bytes(int C, long n_points);
+/* evaluation of image batches (val.py:109-151, medpy binary asd(pred, gt): the mean distance from the surface voxels of pred to the surface of
+ * gt): the sum of sqrt(d^2) over the keys hpfg_surface_distances left in `workspace`, per segment, exact and independent of the order of the
+ * points.  counts_host (HOST memory) and C are those of that call.  sums (device, long long [HPFG_SURFACE_SEGS][2], zeroed by the call):
+ * with x = sqrt((double)d^2), hi = rint(x * 2^19) and lo = (x - hi * 2^-19) * 2^52 (an exact integer, |lo| <= 2^32), sums[s][0] = sum of hi
+ * (read as unsigned), sums[s][1] = sum of lo (signed) over segment s, added with integer atomics: the segment's sum of distances is
+ * sums[s][0] * 2^-19 + sums[s][1] * 2^-52 and the ASD of class c that over counts_host[s] for s = (c - 1) * 2 (pred -> gt).  A segment that is
+ * empty, whose partner is empty (its keys are the 0x7F fill) or that lies beyond 2 (C - 1) is skipped: zeros.  One fill and one launch.
+ * Refuses (-1): a null pointer, C outside 2 .. 16, counts beyond the segments of C classes or 2^31 points, a workspace smaller than
+ * hpfg_surface_workspace_bytes(C, n) or not 16-byte aligned, sums not 8-byte aligned. */
+int hpfg_surface_sums(const void* workspace, long workspace_bytes, int C, const unsigned int* counts_host, long long* sums, void* stream);
 /* Training-time slice augmentation on the device (datasets/utils.py:73-117 RandomGenerator.__call__: random_rot_flip | random_rotate,
  * then scipy zoom(order=0) to the network size, image and mask alike).  The host draws the random parameters in the reference's
  * order and supplies, per sample, the source slice, the rot90/flip or rotation parameters (rotation matrix and offset exactly
