@@ -19,7 +19,7 @@ OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP = 0, 1, 2, 3    
 LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
 LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 138
+VERSION = 139
 RESIZE_TAPS = 36            # HPFG_RESIZE_TAPS: coefficients per output sample and axis of hpfg_resize_cubic's tap tables
 SURFACE_SEGS = 32           # HPFG_SURFACE_SEGS: surface-point segments of hpfg_surface_*, (class - 1) * 2 + side (0 = pred, 1 = gt)
 MATH_F32, MATH_BF16X3 = 0, 1
@@ -219,6 +219,13 @@ PROTOTYPES = {
     "hpfg_attn_keys_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
     "hpfg_attn_keys_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
     "hpfg_attn_keys_scratch_floats": (_l, [_i, _i, _i, _i, _i, _i]),
+    "hpfg_attn_window_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
+    "hpfg_attn_window_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
+    "hpfg_attn_window_scratch_floats": (_l, [_i, _i, _i, _i, _i, _i, _i]),
+    "hpfg_gelu_fwd": (_i, [_p, _p, _l, _p]),
+    "hpfg_gelu_bwd": (_i, [_p, _p, _p, _l, _p]),
+    "hpfg_patch_merge_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "hpfg_patch_merge_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "hpfg_attn_fwd_hd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "hpfg_attn_bwd_hd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "hpfg_gemm_f32": (_i, [_p, _l, _l, _p, _l, _l, _p, _l, _i, _i, _i, _p, _i, _i, _p]),

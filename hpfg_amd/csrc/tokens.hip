@@ -848,6 +848,37 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict
     reinterpret_cast<f32x4*>(out)[i] = reinterpret_cast<const f32x4*>(d)[i] * s[i / per_sample4];
 }
 
+// ---- exact (erf) GELU on its own (Mlp.act of the Swin blocks, reference model/swinunet.py:114-133): 4 floats per lane ---------------------
+__global__ __launch_bounds__(256) void gelu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long total4) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
+    const f32x4 u = reinterpret_cast<const f32x4*>(x)[i];
+    reinterpret_cast<f32x4*>(y)[i] = f32x4{gelu_f(u[0]), gelu_f(u[1]), gelu_f(u[2]), gelu_f(u[3])};
+  }
+}
+
+__global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx, long total4) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
+    const f32x4 u = reinterpret_cast<const f32x4*>(x)[i], d = reinterpret_cast<const f32x4*>(dy)[i];
+    reinterpret_cast<f32x4*>(dx)[i] = f32x4{d[0] * gelu_grad(u[0]), d[1] * gelu_grad(u[1]), d[2] * gelu_grad(u[2]), d[3] * gelu_grad(u[3])};
+  }
+}
+
+// ---- PatchMerging.merging (reference model/swinunet.py:69-75): y[b][i][j][k C + c] = x[b][2 i + k % 2][2 j + k / 2][c], k = 0..3 --------------
+// One index map serves both directions (GATHER: y <- x, else the scatter backward dx <- dy; every element of either side is written once).
+template <bool GATHER>
+__global__ __launch_bounds__(256) void patch_merge_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int H, int W, int C) {
+  const int Q = C / 4, Ho = H / 2, Wo = W / 2;
+  const long total = (long)B * Ho * Wo * 4 * Q;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int c = (int)(e % Q) * 4, k = (int)((e / Q) % 4);
+    const long p = e / (4 * Q);
+    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho), b = (int)(p / ((long)Wo * Ho));
+    const long merged = p * 4 * C + k * C + c, plain = (((long)b * H + 2 * i + k % 2) * W + 2 * j + k / 2) * C + c;
+    if (GATHER) *reinterpret_cast<f32x4*>(dst + merged) = *reinterpret_cast<const f32x4*>(src + plain);
+    else *reinterpret_cast<f32x4*>(dst + plain) = *reinterpret_cast<const f32x4*>(src + merged);
+  }
+}
+
 inline int grid_cap(long total, int cap) {
   long b = (total + 255) / 256;
   if (b < 1) b = 1;
@@ -1087,4 +1118,28 @@ extern "C" int hpfg_scale_rows(const float* d, const float* scale, float* out, i
   const long total4 = (long)B * per_sample / 4;
   hipLaunchKernelGGL(scale_rows_kernel, dim3(grid_cap(total4, 8192)), dim3(256), 0, (hipStream_t)stream, d, scale, out, per_sample / 4, total4);
   return hpfg_launch_status("scale_rows_kernel");
+}
+
+extern "C" int hpfg_gelu_fwd(const float* x, float* y, long n, void* stream) {
+  HPFG_ARG_CHECK(x && y && n > 0 && n % 4 == 0, "gelu_fwd: bad args (n %% 4 == 0)");
+  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_cap(n / 4, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, n / 4);
+  return hpfg_launch_status("gelu_fwd_kernel");
+}
+
+extern "C" int hpfg_gelu_bwd(const float* x, const float* dy, float* dx, long n, void* stream) {
+  HPFG_ARG_CHECK(x && dy && dx && n > 0 && n % 4 == 0, "gelu_bwd: bad args (n %% 4 == 0)");
+  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_cap(n / 4, 8192)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, n / 4);
+  return hpfg_launch_status("gelu_bwd_kernel");
+}
+
+extern "C" int hpfg_patch_merge_fwd(const float* x, float* y, int B, int H, int W, int C, void* stream) {
+  HPFG_ARG_CHECK(x && y && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0 && C >= 4, "patch_merge_fwd: bad args (even H and W, C %% 4 == 0)");
+  hipLaunchKernelGGL(patch_merge_kernel<true>, dim3(grid_cap((long)B * H * W * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C);
+  return hpfg_launch_status("patch_merge_fwd");
+}
+
+extern "C" int hpfg_patch_merge_bwd(const float* dy, float* dx, int B, int H, int W, int C, void* stream) {
+  HPFG_ARG_CHECK(dy && dx && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0 && C >= 4, "patch_merge_bwd: bad args (even H and W, C %% 4 == 0)");
+  hipLaunchKernelGGL(patch_merge_kernel<false>, dim3(grid_cap((long)B * H * W * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, dy, dx, B, H, W, C);
+  return hpfg_launch_status("patch_merge_bwd");
 }

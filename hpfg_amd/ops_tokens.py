@@ -1,5 +1,5 @@
 """Autograd bindings of the token-layout HIP kernels (csrc/tokens.hip) used by the SegFormer branch: LayerNorm, the attention core
-softmax(q k^T) v, and depthwise-3x3 + GELU.  Device tensors only; the library raises if it is missing (no fallback)."""
+softmax(q k^T) v, depthwise-3x3 + GELU, and the shifted-window attention, GELU and patch merging of the Swin blocks (csrc/attn_window.hip).  Device tensors only; the library raises if it is missing (no fallback)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -190,6 +190,124 @@ def attention_for(n_keys: int):
     """The attention op the SegFormer branch uses for ``n_keys`` keys -- a function of the key count alone: ``attention`` up to MAX_KEYS
     (every result at or below 256 x 256 keeps its bits), ``attention_keys`` above."""
     return attention if n_keys <= MAX_KEYS else attention_keys
+
+
+MAX_WINDOW_KEYS = MAX_KEYS          # window^2 tokens of one window are the keys of csrc/attn_window.hip: one 64-key LDS image
+
+
+class _WindowAttention(torch.autograd.Function):
+    """Shifted-window attention (csrc/attn_window.hip): roll, window partition / reverse, the relative-position bias and the shifted-window
+    mask all inside the kernels; gradients to qkv and to the bias table (deterministic partial sums).  Both math modes go through the same
+    two entry points."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias_table, heads, window, shift, scale):
+        lib = L.load()
+        qc, tc = qkv.contiguous().float(), bias_table.contiguous().float()
+        B, H, W, C3 = qc.shape
+        d = C3 // 3 // heads
+        out = torch.empty(B, H, W, C3 // 3, dtype=torch.float32, device=qkv.device)
+        ctx.math = _MATH_CODE[gemm_math()]
+        L.check(lib.hpfg_attn_window_fwd(L.ptr(qc), L.ptr(tc), L.ptr(out), B, H, W, heads, d, window, shift, scale, ctx.math, _st(qkv)), "attn_window_fwd")
+        ctx.save_for_backward(qc, tc)
+        ctx.geo = (heads, d, window, shift, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        qkv, table = ctx.saved_tensors
+        heads, d, window, shift, scale = ctx.geo
+        B, H, W, _ = qkv.shape
+        do = dout.contiguous()
+        dqkv, dtable = torch.empty_like(qkv), torch.empty_like(table)
+        n_scr = lib.hpfg_attn_window_scratch_floats(B, H, W, heads, d, window, ctx.math)
+        if n_scr < 0:
+            L.check(-1, "attn_window_scratch_floats")
+        scratch = torch.empty(n_scr, dtype=torch.float32, device=qkv.device)
+        L.check(lib.hpfg_attn_window_bwd(L.ptr(qkv), L.ptr(table), L.ptr(do), L.ptr(dqkv), L.ptr(dtable), L.ptr(scratch), B, H, W, heads, d, window, shift,
+                                         scale, ctx.math, _st(qkv)), "attn_window_bwd")
+        return dqkv, dtable, None, None, None, None
+
+
+def window_attention(qkv: torch.Tensor, bias_table: torch.Tensor, heads: int, window: int, shift: int, scale: float) -> torch.Tensor:
+    """softmax(scale q k^T + relative-position bias + shifted-window mask) v inside window x window windows of the token map rolled by
+    -shift (WindowAttention.forward of a Swin block between its qkv and proj Linear).  qkv [B,H,W,3C] NHWC as the qkv Linear writes it
+    (channel = t C + head d + p), bias_table [(2 window - 1)^2, heads]; returns [B,H,W,C] with every token's row where the token is.
+    window^2 <= MAX_WINDOW_KEYS, H == W divisible by window, head dim C / heads in HEAD_DIMS, shift 0 or window // 2."""
+    if qkv.dim() != 4 or qkv.shape[-1] % 3:
+        raise ValueError(f"window_attention: qkv {tuple(qkv.shape)} must be [B, H, W, 3 C]")
+    B, H, W, C3 = qkv.shape
+    C_ = C3 // 3
+    if window < 1 or window * window > MAX_WINDOW_KEYS:
+        raise ValueError(f"window_attention: a {window} x {window} window has {window * window} keys; the window kernels take at most "
+                         f"{MAX_WINDOW_KEYS} keys (window <= 8)")
+    if H != W:
+        raise ValueError(f"window_attention: the map must be square (H == W), got {H} x {W}")
+    if H % window or W % window:
+        raise ValueError(f"window_attention: map sides {H} x {W} must be divisible by the window {window}")
+    if heads < 1 or C_ % heads or C_ // heads not in HEAD_DIMS:
+        raise ValueError(f"window_attention: head dim {C_}/{heads} is not built; the HIP attention kernels exist for head dims {HEAD_DIMS}")
+    if shift not in (0, window // 2):
+        raise ValueError(f"window_attention: shift {shift} must be 0 or window // 2 = {window // 2}")
+    if tuple(bias_table.shape) != ((2 * window - 1) ** 2, heads):
+        raise ValueError(f"window_attention: bias_table {tuple(bias_table.shape)} must be [(2 window - 1)^2 = {(2 * window - 1) ** 2}, heads = {heads}]")
+    _need_gpu(qkv, "window_attention")
+    return _WindowAttention.apply(qkv, bias_table, int(heads), int(window), int(shift), float(scale))
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        xc = x.contiguous().float()
+        y = torch.empty_like(xc)
+        L.check(L.load().hpfg_gelu_fwd(L.ptr(xc), L.ptr(y), xc.numel(), _st(x)), "gelu_fwd")
+        ctx.save_for_backward(xc)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        dyc = dy.contiguous()
+        dx = torch.empty_like(x)
+        L.check(L.load().hpfg_gelu_bwd(L.ptr(x), L.ptr(dyc), L.ptr(dx), x.numel(), _st(x)), "gelu_bwd")
+        return dx
+
+
+def gelu(x: torch.Tensor) -> torch.Tensor:
+    """Exact (erf) GELU, nn.GELU(); the element count must be a multiple of 4 (the kernel moves 4 floats per lane)."""
+    if x.numel() == 0 or x.numel() % 4:
+        raise ValueError(f"gelu: {x.numel()} elements; the kernel moves 4 floats per lane, so the count must be a positive multiple of 4")
+    _need_gpu(x, "gelu")
+    return _Gelu.apply(x)
+
+
+class _PatchMerge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        xc = x.contiguous().float()
+        B, H, W, C_ = xc.shape
+        y = torch.empty(B, H // 2, W // 2, 4 * C_, dtype=torch.float32, device=x.device)
+        L.check(L.load().hpfg_patch_merge_fwd(L.ptr(xc), L.ptr(y), B, H, W, C_, _st(x)), "patch_merge_fwd")
+        ctx.geo = (B, H, W, C_)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, H, W, C_ = ctx.geo
+        dyc = dy.contiguous()
+        dx = torch.empty(B, H, W, C_, dtype=torch.float32, device=dy.device)
+        L.check(L.load().hpfg_patch_merge_bwd(L.ptr(dyc), L.ptr(dx), B, H, W, C_, _st(dy)), "patch_merge_bwd")
+        return dx
+
+
+def patch_merge(x: torch.Tensor) -> torch.Tensor:
+    """The 2 x 2 neighbours of NHWC x [B,H,W,C] gathered into [B,H/2,W/2,4C] in the order (0,0), (1,0), (0,1), (1,1) of Swin's
+    PatchMerging; H and W even, C % 4 == 0."""
+    if x.dim() != 4 or x.shape[1] % 2 or x.shape[2] % 2 or x.shape[3] % 4:
+        raise ValueError(f"patch_merge: x {tuple(x.shape)} must be [B, even H, even W, C % 4 == 0]")
+    _need_gpu(x, "patch_merge")
+    return _PatchMerge.apply(x)
 
 
 class _DWGelu(torch.autograd.Function):

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 138
+#define HPFG_VERSION 139
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -496,6 +496,15 @@ int hpfg_resize_bilinear_bwd(const float* dy, float* dx, int B, int h, int w, in
  * branch gradient is dout[b] * scale[b] */
 int hpfg_residual_scale(const float* x, const float* y, const float* scale, float* out, int B, long per_sample, void* stream);
 int hpfg_scale_rows(const float* d, const float* scale, float* out, int B, long per_sample, void* stream);
+/* exact (erf) GELU on its own, 4 floats per lane (Mlp.act of the Swin blocks, reference model/swinunet.py:114-133): y = gelu(x); dx = dy gelu'(x).
+ * n % 4 == 0 */
+int hpfg_gelu_fwd(const float* x, float* y, long n, void* stream);
+int hpfg_gelu_bwd(const float* x, const float* dy, float* dx, long n, void* stream);
+/* PatchMerging.merging (reference model/swinunet.py:69-75) on NHWC x [B,H,W,C], H and W even, C % 4 == 0: y [B,H/2,W/2,4C] with
+ * y[b][i][j][k C + c] = x[b][2 i + k % 2][2 j + k / 2][c] (the reference's concat order x0, x1, x2, x3); the backward scatters dy back, every
+ * element of dx written once */
+int hpfg_patch_merge_fwd(const float* x, float* y, int B, int H, int W, int C, void* stream);
+int hpfg_patch_merge_bwd(const float* dy, float* dx, int B, int H, int W, int C, void* stream);
 /* im2col / col2im of PatchEmbed.proj (segformer.py:172: kernel k, stride s, padding k/2) on NHWC x [B,H,W,C]:
  * cols [B, Ho*Wo, k*k*C] with the patch ordered (u, v, c); col2im is the gather-form transpose (no atomics) */
 int hpfg_im2col_nhwc(const float* x, float* cols, int B, int H, int W, int C, int k, int s, void* stream);
@@ -563,6 +572,29 @@ int hpfg_attn_keys_bwd(const float* q, const float* kv, const float* out, const 
 /* Floats of the backward's scratch for these arguments (reference model/segformer.py:92-128 needs none: autograd keeps the [B,heads,N,M]
  * probabilities instead); -1 with hpfg_last_error set when hpfg_attn_keys_bwd would refuse them. */
 long hpfg_attn_keys_scratch_floats(int B, int N, int M, int heads, int head_dim, int math);
+
+/* ---- shifted-window attention of the Swin blocks (csrc/attn_window.hip; reference model/swinunet.py:207-248) ----------------------------- */
+/* Forward (reference model/swinunet.py:207-248, WindowAttention.forward between the qkv and the proj Linear): per (image, window, head)
+ * out = softmax(scale q k^T + bias_table[idx][head] + mask) v over the window x window tokens of each window of the map rolled by -shift.
+ * qkv [B,H,W,3C] is the qkv Linear's output (channel = t C + head head_dim + p, t = q, k, v; C = heads head_dim), bias_table
+ * [(2 window - 1)^2, heads], out [B,H,W,C] (channel = head head_dim + p).  Roll, window partition, window reverse and the roll back are
+ * addressing: position (i, j) of window (wy, wx) is the token ((wy window + i + shift) mod H, (wx window + j + shift) mod W), read and
+ * written there; idx = (i1 - i2 + window - 1)(2 window - 1) + (j1 - j2 + window - 1); with shift > 0 the mask is the reference's literal
+ * -100 between positions whose rolled coordinates lie in different regions (0 below H - window, 1 below H - shift, else 2, per axis).
+ * window^2 <= 64, H % window == 0, W % window == 0, 0 <= shift < window, head_dim 32 or 64, heads >= 1; math = HPFG_MATH_BF16X3
+ * (split-bf16 MFMA products; with shift 0 and a zero table the operation sequence of hpfg_attn_mfma_fwd_hd per window) or HPFG_MATH_F32
+ * (exact fp32).  Returns -1 and sets hpfg_last_error on anything else or a null pointer. */
+int hpfg_attn_window_fwd(const float* qkv, const float* bias_table, float* out, int B, int H, int W, int heads, int head_dim, int window, int shift,
+                         float scale, int math, void* stream);
+/* Backward of the above (reference model/swinunet.py:207-248 under autograd): dqkv like qkv, through the same addressing, every element
+ * written exactly once; dbias like bias_table, dbias[idx][head] = sum of dS over images, windows and the pairs of that idx, from
+ * per-workgroup partials added in a fixed order (no atomics: bit-identical from run to run).  scratch: hpfg_attn_window_scratch_floats(...)
+ * floats.  No pointer may be null. */
+int hpfg_attn_window_bwd(const float* qkv, const float* bias_table, const float* dout, float* dqkv, float* dbias, float* scratch, int B, int H, int W,
+                         int heads, int head_dim, int window, int shift, float scale, int math, void* stream);
+/* Floats of the backward's scratch (the bias-gradient partials; reference model/swinunet.py:207-248 needs none: autograd scatter-adds into the
+ * table); -1 with hpfg_last_error set when hpfg_attn_window_bwd would refuse the shape. */
+long hpfg_attn_window_scratch_floats(int B, int H, int W, int heads, int head_dim, int window, int math);
 
 /* ---- projection necks + Dense_Loss (UNet_Plus; reference model/unet.py:120-152, utils/loss/dense_loss.py:17-40) ------------------------ */
 /* C[m,n] = act(sum_k A(m,k) B(k,n) + bias[n]) in exact fp32 on the matrix cores; A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn], C row-major
