@@ -1,70 +1,14 @@
 // Attention core of the SegFormer branch on the matrix cores (reference model/segformer.py:92-128, Attention.forward after the q / kv
 // projections and the spatial reduction):   out = softmax(scale * q k^T) v   per (image, head), head dim D = 32 or 64 (every kernel is a template over D), at most 64 keys.
 //
-// (65 .. 256 keys -- inputs above 256 x 256 -- are served by attn_keys.hip, which walks the keys in blocks of 64 with the LDS images and fragment
-// helpers of this file: attn_frag.h holds what the two share.)
-//
-// Every product is split-bf16 ("bf16x3": hi*hi + hi*lo + lo*hi, fp32 accumulate) on v_mfma_f32_16x16x32_bf16, like the convolutions.
-// Head dim 32 is exactly one MFMA k-step, so a 16 x 16 score tile costs three MFMAs; head dim 64 (MiT-B1 and wider) is two k-steps, six
-// MFMAs, and P V / dS K / dV / dK produce four 16-row d-tiles instead of two.  Two facts keep the kernels free of LDS transposes of the
-// probabilities:
-//   * Q, K, V and dO fragments all have the same lane layout (row or column = lane & 15, 8 consecutive head-dim elements of k-group
-//     lane >> 4), so the SAME registers give S^T = K Q^T (keys on the accumulator rows, the query on the lane) or S = Q K^T (queries on
-//     the rows, the key on the lane) just by swapping the MFMA arguments.
-//   * An accumulator tile feeds the next MFMA as its B operand directly (MI355X guide, "accumulator tile as the next MFMA's operand"):
-//     the 8 contraction positions of a lane are its 4 accumulator rows of tile 2s and its 4 rows of tile 2s + 1; the OTHER operand (V^T,
-//     K^T, dO^T, Q^T from LDS) is gathered in that same permuted order, which costs two 8-byte LDS reads instead of one 16-byte read.
-// Forward and dQ use the S^T orientation (softmax statistics are then a 16-value reduction in registers plus two cross-lane steps);
-// dK / dV use the S orientation and accumulate over all queries of a workgroup in registers; per-workgroup partials are summed in a fixed
-// order by attn_dkv_sum_kernel (deterministic, no atomics).
+// The arithmetic, lane layouts, LDS images and every phase of the kernels are in attn_core.h, shared with attn_keys.hip (65 .. 256 keys --
+// inputs above 256 x 256) and attn_window.hip.  This file's own: one LDS image of all keys staged once per workgroup, no logit term,
+// the dK / dV kernel (its whole text: dK / dV are not among the shared phases) with its fragments held in registers at D = 32, and
+// per-workgroup dK / dV partials summed in a fixed order by attn_dkv_sum_kernel.
 //   q [B,N,heads,D], kv [B,M,2,heads,D] (the kv Linear's output layout), out / dq like q, dkv like kv.
-// LDS rows: a natural [64 keys][D d] bf16 image has rows of 2 D + 16 bytes (80 / 144), a transposed [D d][64 keys] image rows of 144 bytes.
-// Both strides are 4 (mod 16) dwords -- 20 and 36 -- so the 16 rows of a 16-byte fragment read start at 16 distinct multiples of 4 dwords
-// and cover the 64 banks once; the 8-byte reads of the transposed images (row stride 36 dwords, + 2 dwords per k-group) are conflict-free
-// within each half wave if the hardware serves them half wave by half wave.  This is bank arithmetic, not a measurement: no LDS conflict
-// counter was read for these kernels.  Not analysed at all: the 2-byte scalar stores that write a transposed image in stage_kv (stride
-// TROW between a thread's 8 stores; one pass at D = 32, two at D = 64) -- staging runs once per workgroup.  The 16-byte pad stays at D = 64
-// on that reasoning; what was measured is the kernels' time against equal-work D = 32 launches.
-#include "attn_frag.h"
+#include "attn_core.h"
 
 namespace {
-
-// S^T tiles (keys on rows) of 16 queries -> probabilities p[t][r] of key 16 t + 4 g + r for the query on this lane (lane & 15)
-template <int D>
-__device__ __forceinline__ void softmax_t(const unsigned char* ldsK, const a_bf16x8 (&qh)[Geo<D>::KS], const a_bf16x8 (&ql)[Geo<D>::KS], int M, int lane,
-                                          f32x4 (&p)[4]) {
-  const int g = lane >> 4;
-  float mx = NEG;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    p[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < Geo<D>::KS; ++ks) {
-      const a_bf16x8 kh = nat_frag<D>(ldsK, 16 * t, ks, lane), kl = nat_frag<D>(ldsK + Geo<D>::KPLANE, 16 * t, ks, lane);
-      ATT_MFMA3(p[t], kh, kl, qh[ks], ql[ks])
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (16 * t + 4 * g + r >= M) p[t][r] = NEG;
-      mx = fmaxf(mx, p[t][r]);
-    }
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 16));
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  float den = 0.f;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[t][r] = 16 * t + 4 * g + r < M ? expf(p[t][r] - mx) : 0.f;
-      den += p[t][r];
-    }
-  den += __shfl_xor(den, 16);
-  den += __shfl_xor(den, 32);
-  const float inv = 1.f / den;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) p[t] *= inv;
-}
 
 template <int D>
 __global__ __launch_bounds__(256) void attn_mfma_fwd_kernel(const float* __restrict__ q, const float* __restrict__ kv, float* __restrict__ out, int N, int M,
@@ -81,26 +25,11 @@ __global__ __launch_bounds__(256) void attn_mfma_fwd_kernel(const float* __restr
   const long qi = (long)blockIdx.x * 64 + wave * 16 + (lane & 15);
   a_bf16x8 qh[KS], ql[KS];
   load_row_frags<D>(q + (long)b * N * C, qi, N, C, h, lane, scale, qh, ql);
-  f32x4 p[4];
-  softmax_t<D>(ldsK, qh, ql, M, lane, p);
-  f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    a_bf16x8 ph, pl;
-    acc_operand(p[2 * s], p[2 * s + 1], ph, pl);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      const a_bf16x8 vh = trn_frag(ldsVT, TROW, 16 * dt, s, lane), vl = trn_frag(ldsVT + TPL, TROW, 16 * dt, s, lane);
-      ATT_MFMA3(o[dt], vh, vl, ph, pl)          // O^T[d][q]
-    }
-  }
-  if (qi < N) {
-    float* op = out + ((long)b * N + qi) * C + h * D + (lane >> 4) * 4;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt];
-  }
+  f32x4 p[4], o[DT];
+  softmax_t<D>(ldsK, qh, ql, M, lane, NoTerm{}, p);
+  zero_tiles(o);
+  mul_trn<D>(p, ldsVT, lane, o);               // O^T[d][q]
+  if (qi < N) store_o<D>(out + ((long)b * N + qi) * C + h * D + (lane >> 4) * 4, o);
 }
 
 // dq = scale * dS K with dS = P .* (dP - rowsum(P .* dP)), dP = dO V^T   (S^T orientation, one query per lane)
@@ -121,50 +50,20 @@ __global__ __launch_bounds__(256) void attn_mfma_dq_kernel(const float* __restri
   a_bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
   load_row_frags<D>(q + (long)b * N * C, qi, N, C, h, lane, scale, qh, ql);
   load_row_frags<D>(dout + (long)b * N * C, qi, N, C, h, lane, 1.f, dh, dl);
-  f32x4 p[4], dp[4];
-  softmax_t<D>(ldsK, qh, ql, M, lane, p);
-  float delta = 0.f;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const a_bf16x8 vh = nat_frag<D>(ldsV, 16 * t, ks, lane), vl = nat_frag<D>(ldsV + KPLANE, 16 * t, ks, lane);
-      ATT_MFMA3(dp[t], vh, vl, dh[ks], dl[ks])  // dP^T[key][q]
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) delta += p[t][r] * dp[t][r];
-  }
-  delta += __shfl_xor(delta, 16);
-  delta += __shfl_xor(delta, 32);
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dp[t][r] = p[t][r] * (dp[t][r] - delta);          // dS^T
-  f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    a_bf16x8 sh, sl;
-    acc_operand(dp[2 * s], dp[2 * s + 1], sh, sl);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      const a_bf16x8 kh = trn_frag(ldsKT, TROW, 16 * dt, s, lane), kl = trn_frag(ldsKT + TPL, TROW, 16 * dt, s, lane);
-      ATT_MFMA3(o[dt], kh, kl, sh, sl)          // dQ^T[d][q] / scale
-    }
-  }
-  if (qi < N) {
-    float* op = dq + ((long)b * N + qi) * C + h * D + g * 4;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt] * scale;
-  }
+  f32x4 p[4], dp[4], o[DT];
+  softmax_t<D>(ldsK, qh, ql, M, lane, NoTerm{}, p);
+  ds_t<D>(ldsV, dh, dl, lane, p, dp);              // dS^T
+  zero_tiles(o);
+  mul_trn<D>(dp, ldsKT, lane, o);              // dQ^T[d][q] / scale
+  if (qi < N) store_o<D>(dq + ((long)b * N + qi) * C + h * D + g * 4, o, scale);
 }
 
 // dV = P^T dO, dK = scale * dS^T Q over the queries [q0, q1) of this workgroup (S orientation: 4 queries per lane, the key on the lane).
 // Each wave takes 32 queries per step; the transposed images dO^T / Q^T [D d][32 q] of those queries live in a per-wave LDS slot.
 // The K / V fragments with the key on the lane are constant over the loop: at D = 32 they stay in registers (64 VGPRs); at D = 64 they
 // would take 128 next to 128 accumulator registers, so they are re-read from LDS at every step instead (HOLD = false).
+// The loop body and the wave reduction exist again, edited, in attn_keys_dkv_kernel and attn_window_dkv_kernel (see the top of attn_core.h
+// for why they are not shared phases): an edit here is made there too.
 template <int D>
 __global__ __launch_bounds__(256) void attn_mfma_dkv_kernel(const float* __restrict__ q, const float* __restrict__ kv, const float* __restrict__ dout,
                                                             float* __restrict__ part, int N, int M, int heads, float scale, int q_per_block) {
@@ -339,8 +238,6 @@ __global__ __launch_bounds__(256) void attn_dkv_sum_kernel(const float* __restri
     dkv[(((long)b * M + key) * 2 + which) * C + h * D + d] = s;
   }
 }
-
-constexpr int Q_PER_BLOCK = 512;                 // queries per dK / dV workgroup (a multiple of 128: four waves x 32)
 
 template <int D>
 int launch_fwd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, float scale, hipStream_t st) {

@@ -1,5 +1,5 @@
-// Fragment helpers shared by the attention kernels on the matrix cores: csrc/attn.hip (at most 64 keys, one LDS image) and
-// csrc/attn_keys.hip (up to 256 keys, walked in blocks of 64 with the same LDS images).  The lane layouts are documented at the top of attn.hip.
+// Fragment helpers of the attention kernels on the matrix cores: the LDS image geometry, the split-bf16 conversion and the fragment loaders.
+// attn_core.h builds the kernels' phases on them and documents the lane layouts at its top.
 #pragma once
 #include "common.h"
 
@@ -10,7 +10,7 @@ typedef __bf16 a_bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 a_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float a_f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int MK = 64;                         // keys of one LDS image (attn.hip: the maximum; attn_keys.hip: one key block)
+constexpr int MK = 64;                         // keys of one LDS image (attn.hip, attn_window.hip: the maximum; attn_keys.hip: one key block)
 constexpr int TROW = 144;                      // bytes per row of a [D d][64 keys] bf16 image (128 B + 16 B pad)
 constexpr int QROW = 80;                       // bytes per row of a per-wave [D d][32 q] bf16 image (64 B + 16 B pad)
 template <int D> struct Geo {
@@ -41,6 +41,7 @@ __device__ __forceinline__ void split8v(const float (&v)[8], a_bf16x8& hi, a_bf1
   ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AL, BH, ACC, 0, 0, 0); \
   ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, BL, ACC, 0, 0, 0);
 
+// (stage_win of attn_window.hip is this text with the window's token table; why the two are not one function: top of attn_core.h)
 // rows [key][D d] of k or v (which = 0 / 1) of one (image, head) -> natural image [64][D] (hi, lo) and / or transposed image [D][64].
 // The image holds keys key0 .. key0 + 63 of the M keys (key0 = 0 in attn.hip); rows of keys >= M are zeros and are never loaded.
 template <int D>

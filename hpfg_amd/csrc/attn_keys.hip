@@ -2,8 +2,8 @@
 // reduction):   out = softmax(scale * q k^T) v   per (image, head), head dim D = 32 or 64.  A MiT stage has (H / 32) (W / 32) keys, so the
 // one-image kernels of attn.hip (at most 64 keys) stop at 256 x 256 inputs; these serve up to 512 x 512.
 //
-// Same arithmetic, lane layouts and LDS images as attn.hip (attn_frag.h): split-bf16 products on v_mfma_f32_16x16x32_bf16, S^T orientation
-// for forward and dQ, S orientation for dK / dV.  The keys are walked in blocks of 64, one LDS image at a time:
+// The arithmetic, lane layouts, LDS images and phases are those of attn_core.h.  This file's own is the walk over the keys in blocks of 64,
+// one LDS image at a time:
 //   * forward: all NB = ceil(M / 64) <= 4 blocks' score tiles of a query stay in registers (16 NB values per lane), so the softmax is the
 //     exact two-pass one (max, exp, sum, one reciprocal) -- no online rescaling; then P V accumulates block by block in key order.  Masked
 //     positions are exact zeros, so for M <= 64 (NB = 1) the operation sequence, hence every bit of `out`, is that of attn_mfma_fwd_kernel.
@@ -15,12 +15,11 @@
 // LDS: the images of attn.hip, one key block at a time -- forward 20 / 36 KB, dQ 29 / 54 KB, dK / dV 60 / 116 KB at D = 32 / 64.
 // HPFG_MATH=f32: thread-per-query fp32 kernels over the same key blocks (scores are recomputed in a second pass instead of being kept:
 // 256 of them would not fit a thread's registers); dK / dV through hpfg_gemm_f32 like the <= 64-key path.
-#include "attn_frag.h"
+#include "attn_core.h"
 
 namespace {
 
 constexpr int KEYS_MAX = 256;
-constexpr int Q_PER_BLOCK = 512;                 // queries per dK / dV workgroup (a multiple of 128: four waves x 32)
 
 // NB x 64 keys; lse may be null (inference)
 template <int D, int NB>
@@ -36,70 +35,30 @@ __global__ __launch_bounds__(256) void attn_keys_fwd_kernel(const float* __restr
   a_bf16x8 qh[KS], ql[KS];
   load_row_frags<D>(q + (long)b * N * C, qi, N, C, h, lane, scale, qh, ql);
   // S^T tiles of every key block: p[4 kb + t][r] = score of key 64 kb + 16 t + 4 g + r for the query on this lane
-  f32x4 p[4 * NB];
-  float mx = NEG;
+  f32x4 p[4 * NB], o[DT];
+  float mx = NEG, den;
 #pragma unroll
   for (int kb = 0; kb < NB; ++kb) {
     if (kb) __syncthreads();                    // every wave is done with the previous K image
     stage_kv<D>(kv, b, h, M, C, 0, ldsK, nullptr, tid, 64 * kb);
     if (kb == 0) stage_kv<D>(kv, b, h, M, C, 1, nullptr, ldsVT, tid, 0);
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      f32x4& s = p[4 * kb + t];
-      s = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const a_bf16x8 kh = nat_frag<D>(ldsK, 16 * t, ks, lane), kl = nat_frag<D>(ldsK + KPLANE, 16 * t, ks, lane);
-        ATT_MFMA3(s, kh, kl, qh[ks], ql[ks])
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (64 * kb + 16 * t + 4 * g + r >= M) s[r] = NEG;
-        mx = fmaxf(mx, s[r]);
-      }
-    }
+    scores_t<D>(ldsK, qh, ql, 64 * kb, M, lane, NoTerm{}, p + 4 * kb, mx);
   }
-  mx = fmaxf(mx, __shfl_xor(mx, 16));
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  float den = 0.f;
+  softmax_finish_t<4 * NB>(p, M, lane, mx, den);
+  zero_tiles(o);
+  // block 0, whose V^T image was staged beside its K image, then blocks 1 .. NB - 1.  Not one loop over all blocks with `if (kb)` around
+  // the restaging: built on the shared phases that form cost <32, 1> a wave per SIMD (profiles/attn_core_resources.txt)
+  mul_trn<D>(p, ldsVT, lane, o);                 // O^T[d][q]
 #pragma unroll
-  for (int t = 0; t < 4 * NB; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[t][r] = 16 * t + 4 * g + r < M ? expf(p[t][r] - mx) : 0.f;
-      den += p[t][r];
-    }
-  den += __shfl_xor(den, 16);
-  den += __shfl_xor(den, 32);
-  const float inv = 1.f / den;
-#pragma unroll
-  for (int t = 0; t < 4 * NB; ++t) p[t] *= inv;
-  f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int kb = 0; kb < NB; ++kb) {
-    if (kb) {
-      __syncthreads();                          // every wave is done with the previous V^T image
-      stage_kv<D>(kv, b, h, M, C, 1, nullptr, ldsVT, tid, 64 * kb);
-      __syncthreads();
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      a_bf16x8 ph, pl;
-      acc_operand(p[4 * kb + 2 * s], p[4 * kb + 2 * s + 1], ph, pl);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const a_bf16x8 vh = trn_frag(ldsVT, TROW, 16 * dt, s, lane), vl = trn_frag(ldsVT + TPL, TROW, 16 * dt, s, lane);
-        ATT_MFMA3(o[dt], vh, vl, ph, pl)          // O^T[d][q]
-      }
-    }
+  for (int kb = 1; kb < NB; ++kb) {
+    __syncthreads();                            // every wave is done with the previous V^T image
+    stage_kv<D>(kv, b, h, M, C, 1, nullptr, ldsVT, tid, 64 * kb);
+    __syncthreads();
+    mul_trn<D>(p + 4 * kb, ldsVT, lane, o);
   }
   if (qi < N) {
-    float* op = out + ((long)b * N + qi) * C + h * D + g * 4;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt];
+    store_o<D>(out + ((long)b * N + qi) * C + h * D + g * 4, o);
     if (lse && g == 0) lse[((long)b * heads + h) * N + qi] = mx + logf(den);
   }
 }

@@ -1,7 +1,7 @@
 // Shifted-window attention of the Swin blocks (reference model/swinunet.py:207-248, WindowAttention.forward between the qkv and the proj
 // Linear):   out = softmax(scale * q k^T + bias + mask) v   per (image, window, head), head dim D = 32 or 64, windows of w x w tokens with
-// w^2 <= 64 keys (49 at w = 7) -- the ranges attn.hip was built for, so the arithmetic, lane layouts and LDS images are those of attn.hip
-// (attn_frag.h): split-bf16 products on v_mfma_f32_16x16x32_bf16, S^T orientation for forward and dQ, S orientation for dK / dV.
+// w^2 <= 64 keys (49 at w = 7) -- the ranges attn.hip was built for, so the arithmetic, lane layouts, LDS images and phases are those of
+// attn_core.h; this file's own is the window addressing (token table), the logit term (bias + mask) and the bias gradient.
 //
 // One workgroup per (window, head, image).  What the reference does as four tensor copies per block -- roll by -s, window partition,
 // window reverse, roll by +s -- is addressing here: position l = i w + j of window (wy, wx) is the rolled coordinate (y', x') =
@@ -18,8 +18,8 @@
 // LDS, one thread per idx adds the <= w^2 pairs in a fixed order into a per-workgroup partial, and attn_window_dbias_sum_kernel adds the
 // partials in a fixed order (four contiguous slices, then ((0 + 1) + 2) + 3).  No atomics: two runs give the same bits.
 // HPFG_MATH_F32: one thread per query / per key in plain fp32 (scores kept in LDS rows), same addressing, same partial scheme.
-// LDS rows as in attn.hip (strides of 4 mod 16 dwords); the dS tile has rows of 65 floats (a lane's row starts one bank after its neighbour's).
-#include "attn_frag.h"
+// LDS rows as in attn_core.h (strides of 4 mod 16 dwords); the dS tile has rows of 65 floats (a lane's row starts one bank after its neighbour's).
+#include "attn_core.h"
 
 namespace {
 
@@ -64,7 +64,16 @@ __device__ __forceinline__ float logit_add(float sc, int rq, int rk, int c0, con
   return (sc + bias[(rq & 0xFFFF) - (rk & 0xFFFF) + c0]) + m;
 }
 
-// stage_kv of attn_frag.h with the window's token table: channels [coff, coff + D) of the tokens tok[0..63] of image base `img` ([HW][C3])
+// the logit term of attn_core.h for the one query of a lane, whose word rq was loaded once: bias + mask of the logit against key position kp
+struct WinTerm {
+  int rq;
+  const int* rel;
+  const float* bias;
+  int c0;
+  __device__ __forceinline__ float operator()(float sc, int kp) const { return logit_add(sc, rq, rel[kp], c0, bias); }
+};
+
+// stage_kv of attn_core.h with the window's token table: channels [coff, coff + D) of the tokens tok[0..63] of image base `img` ([HW][C3])
 template <int D, int NT>
 __device__ __forceinline__ void stage_win(const float* __restrict__ img, const int* tok, int C3, int coff, unsigned char* nat, unsigned char* trn, int tid) {
   constexpr int KROW = Geo<D>::KROW, KPLANE = Geo<D>::KPLANE, TPL = Geo<D>::TPL;
@@ -94,44 +103,6 @@ __device__ __forceinline__ void stage_win(const float* __restrict__ img, const i
   }
 }
 
-// softmax_t of attn.hip with the bias and the mask added to the scores: p[t][r] of key 16 t + 4 g + r for the query l1 on this lane
-template <int D>
-__device__ __forceinline__ void softmax_w(const unsigned char* ldsK, const a_bf16x8 (&qh)[Geo<D>::KS], const a_bf16x8 (&ql)[Geo<D>::KS], int L, int lane,
-                                          int rq, const int* rel, const float* bias, int c0, f32x4 (&p)[4]) {
-  const int g = lane >> 4;
-  float mx = NEG;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    p[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < Geo<D>::KS; ++ks) {
-      const a_bf16x8 kh = nat_frag<D>(ldsK, 16 * t, ks, lane), kl = nat_frag<D>(ldsK + Geo<D>::KPLANE, 16 * t, ks, lane);
-      ATT_MFMA3(p[t], kh, kl, qh[ks], ql[ks])
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int key = 16 * t + 4 * g + r;
-      p[t][r] = key < L ? logit_add(p[t][r], rq, rel[key], c0, bias) : NEG;
-      mx = fmaxf(mx, p[t][r]);
-    }
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 16));
-  mx = fmaxf(mx, __shfl_xor(mx, 32));
-  float den = 0.f;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[t][r] = 16 * t + 4 * g + r < L ? expf(p[t][r] - mx) : 0.f;
-      den += p[t][r];
-    }
-  den += __shfl_xor(den, 16);
-  den += __shfl_xor(den, 32);
-  const float inv = 1.f / den;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) p[t] *= inv;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ table, float* __restrict__ out, Win gm,
                                                               float scale) {
@@ -154,26 +125,11 @@ __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const float* __res
   const int l1 = wave * 16 + (lane & 15), t1 = tok[l1];
   a_bf16x8 qh[KS], ql[KS];
   load_row_frags<D>(img, t1 >= 0 ? t1 : HW, HW, C3, h, lane, scale, qh, ql);
-  f32x4 p[4];
-  softmax_w<D>(ldsK, qh, ql, gm.L(), lane, rel[l1], rel, bias, gm.c0(), p);
-  f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    a_bf16x8 ph, pl;
-    acc_operand(p[2 * s], p[2 * s + 1], ph, pl);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      const a_bf16x8 vh = trn_frag(ldsVT, TROW, 16 * dt, s, lane), vl = trn_frag(ldsVT + TPL, TROW, 16 * dt, s, lane);
-      ATT_MFMA3(o[dt], vh, vl, ph, pl)          // O^T[d][q]
-    }
-  }
-  if (t1 >= 0) {
-    float* op = out + ((long)b * HW + t1) * C + h * D + (lane >> 4) * 4;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt];
-  }
+  f32x4 p[4], o[DT];
+  softmax_t<D>(ldsK, qh, ql, gm.L(), lane, WinTerm{rel[l1], rel, bias, gm.c0()}, p);
+  zero_tiles(o);
+  mul_trn<D>(p, ldsVT, lane, o);                  // O^T[d][q]
+  if (t1 >= 0) store_o<D>(out + ((long)b * HW + t1) * C + h * D + (lane >> 4) * 4, o);
 }
 
 // this workgroup's part[idx] = sum of ds[l1][l2] over the pairs of the window with bias index idx, in a fixed order (l2 ascending)
@@ -216,47 +172,16 @@ __global__ __launch_bounds__(256) void attn_window_dq_kernel(const float* __rest
   a_bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
   load_row_frags<D>(img, t1 >= 0 ? t1 : HW, HW, C3, h, lane, scale, qh, ql);
   load_row_frags<D>(dout + (long)b * HW * C, t1 >= 0 ? t1 : HW, HW, C, h, lane, 1.f, dh, dl);
-  f32x4 p[4], dp[4];
-  softmax_w<D>(ldsK, qh, ql, gm.L(), lane, rel[l1], rel, bias, gm.c0(), p);
-  float delta = 0.f;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const a_bf16x8 vh = nat_frag<D>(ldsV, 16 * t, ks, lane), vl = nat_frag<D>(ldsV + KPLANE, 16 * t, ks, lane);
-      ATT_MFMA3(dp[t], vh, vl, dh[ks], dl[ks])  // dP^T[key][q]
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) delta += p[t][r] * dp[t][r];
-  }
-  delta += __shfl_xor(delta, 16);
-  delta += __shfl_xor(delta, 32);
+  f32x4 p[4], dp[4], o[DT];
+  softmax_t<D>(ldsK, qh, ql, gm.L(), lane, WinTerm{rel[l1], rel, bias, gm.c0()}, p);
+  ds_t<D>(ldsV, dh, dl, lane, p, dp);              // dS^T: zero at the padding keys (p = 0) and padding queries (dO = 0)
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dp[t][r] = p[t][r] * (dp[t][r] - delta);          // dS^T: zero at the padding keys (p = 0) and padding queries (dO = 0)
-      dsl[l1 * DSROW + 16 * t + 4 * g + r] = dp[t][r];
-    }
-  f32x4 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    a_bf16x8 sh, sl;
-    acc_operand(dp[2 * s], dp[2 * s + 1], sh, sl);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      const a_bf16x8 kh = trn_frag(ldsKT, TROW, 16 * dt, s, lane), kl = trn_frag(ldsKT + TPL, TROW, 16 * dt, s, lane);
-      ATT_MFMA3(o[dt], kh, kl, sh, sl)          // dQ^T[d][q] / scale
-    }
-  }
-  if (t1 >= 0) {
-    float* op = dqkv + ((long)b * HW + t1) * C3 + h * D + g * 4;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<f32x4*>(op + 16 * dt) = o[dt] * scale;
-  }
+    for (int r = 0; r < 4; ++r) dsl[l1 * DSROW + 16 * t + 4 * g + r] = dp[t][r];
+  zero_tiles(o);
+  mul_trn<D>(dp, ldsKT, lane, o);                 // dQ^T[d][q] / scale
+  if (t1 >= 0) store_o<D>(dqkv + ((long)b * HW + t1) * C3 + h * D + g * 4, o, scale);
   __syncthreads();
   bias_partial<256>(dsl, gm, part + (((long)b * gridDim.x + win) * gm.heads + h) * gm.T(), tid);
 }
