@@ -367,12 +367,14 @@ __global__ __launch_bounds__(256) void bn_eval_table_kernel(const float* __restr
                                                             float* __restrict__ bn, int C) {
   int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  float rstd = 1.f / sqrtf(rv[c] + eps);
-  float scale = gamma[c] * rstd;
+  // fp64 with ONE rounding per row, like the train-mode coefficients (hpfg_bn_coef): a chain of fp32 roundings (var + eps, sqrt, 1 / x,
+  // * gamma, mean * scale, beta - ...) left rstd 1.5, scale 1.8 and shift 2 ulp from the exact rows (tests/test_gpu_bn_acc.py)
+  const double rstd = 1.0 / sqrt((double)rv[c] + (double)eps);
+  const double scale = (double)gamma[c] * rstd;
   bn[HPFG_BN_MEAN * C + c] = rm[c];
-  bn[HPFG_BN_RSTD * C + c] = rstd;
-  bn[HPFG_BN_SCALE * C + c] = scale;
-  bn[HPFG_BN_SHIFT * C + c] = beta[c] - rm[c] * scale;
+  bn[HPFG_BN_RSTD * C + c] = (float)rstd;
+  bn[HPFG_BN_SCALE * C + c] = (float)scale;
+  bn[HPFG_BN_SHIFT * C + c] = (float)((double)beta[c] - (double)rm[c] * scale);
 }
 
 }  // namespace

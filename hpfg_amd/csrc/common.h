@@ -54,17 +54,21 @@ __host__ __device__ static inline bool hpfg_keep(uint32_t i, uint32_t seed, uint
 __device__ static inline float lrelu(float y) { return fmaxf(y, HPFG_LEAKY * y); }   // == y > 0 ? y : 0.01*y
 
 // ---- BatchNorm sums through integer atomics (HpfgConvArgs.stat_acc / HpfgAct.bn_acc) ----------------------------------------------------
-// A producer workgroup adds its per-channel partial sums to the layer accumulator, long long [SHARDS][which][limb][C]; every consumer reads
-// the 8 shards of its channels and derives the BatchNorm coefficients itself, so no finalize launch sits between the two kernels.  The
-// split t = hi + lo * 2^-52 (hi = rint(t), lo = (t - hi) * 2^52: both exact for a float t above 2^-29; |lo| <= 2^51, so 2^11 partial sums add
-// without overflow -- every launcher that takes an accumulator checks its workgroups per shard against that: HPFG_ACC_CHECK) loses nothing an fp64 sum would keep, and integer sums are associative: bit-reproducible totals without a fixed
-// workgroup order (a float atomic would make BatchNorm, hence the run, non-deterministic).
-// host-side guard of that bound, for every launcher that accepts a sum accumulator: `workgroups` partial sums spread over `shards` shards
+// A producer workgroup adds its per-channel partial sums to the layer accumulator, long long [shard][which][C][limb]; every consumer reads
+// the shards of its channels and derives the BatchNorm coefficients itself, so no finalize launch sits between the two kernels.  The
+// split t = hi + lo * 2^-52 (hi = rint(t), lo = (t - hi) * 2^52: both exact for a float t above 2^-29; |lo| <= 2^51) loses nothing an fp64
+// sum would keep, and integer sums are associative: bit-reproducible totals without a fixed workgroup order (a float atomic would make
+// BatchNorm, hence the run, non-deterministic).
+// Overflow: the reader (hpfg_acc_read2) adds the shards' limbs in int64 BEFORE it converts, so what must stay below 2^63 is the low limb of
+// ALL shards together: 2^11 partial sums per accumulator and pass (2^11 * 2^51 = 2^62), however many shards they are spread over -- sharding
+// relieves the same-address contention, it does not raise the bound.
+// host-side guard of that bound, for every launcher that accepts a sum accumulator: the launch's `workgroups` (one hpfg_acc_add per channel
+// and sum each) are ALL the adds its accumulator receives before it is read and zeroed again
 #define HPFG_ACC_MAX_ADDS 2048
-#define HPFG_ACC_CHECK(workgroups, shards, who)                                                                                     \
-  HPFG_ARG_CHECK(((long)(workgroups) + (shards) - 1) / ((shards) > 0 ? (shards) : 1) <= HPFG_ACC_MAX_ADDS,                           \
-                 "%s: %ld workgroups on %d accumulator shards exceed the %d exact adds per shard of hpfg_acc_add", who, (long)(workgroups), (int)(shards), \
-                 HPFG_ACC_MAX_ADDS)
+#define HPFG_ACC_CHECK(workgroups, shards, who)                                                                                          \
+  HPFG_ARG_CHECK((long)(workgroups) <= HPFG_ACC_MAX_ADDS,                                                                                 \
+                 "%s: %ld workgroups (on %d accumulator shards) exceed the %d adds whose low limbs hpfg_acc_read2 can sum in 64 bits", who, \
+                 (long)(workgroups), (int)(shards), HPFG_ACC_MAX_ADDS)
 __device__ __forceinline__ void hpfg_acc_add(long long* acc, int C, int shard, int which, int c, float t) {
   const float r = rintf(t);
   const long long hi = (long long)r, lo = (long long)rintf((t - r) * 4503599627370496.f);

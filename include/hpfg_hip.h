@@ -110,7 +110,8 @@ typedef struct HpfgConvArgs {
                            totals are bit-reproducible whatever order the workgroups finish in.  Shard = workgroup id % stat_shards: more
                            shards = less same-address contention among the producer's workgroups (1 shard of a 768-workgroup launch: +40 us),
                            fewer = less to read in every consumer workgroup's prologue (32 bytes per channel and shard).
-                           The accumulator must be zero when the launch starts (hpfg_pack_weights_bump zeroes a region). */
+                           The accumulator must be zero when the launch starts (hpfg_pack_weights_bump zeroes a region).  A launch of
+                           more than 2048 workgroups is refused: the readers add the low limbs of all shards in 64 bits. */
   int32_t stat_shards;  /* power of two, 1 .. HPFG_ACC_MAX_SHARDS */
   int32_t reserved2;
   float* stage_out;     /* optional, 3x3 layers on the bf16x3 kernels with a non-PLAIN source of (a0.C + a1.C) % 8 == 0 channels at sizes that are

@@ -64,7 +64,9 @@ class AdHocConv:
         self._keep = (d, dev_tab)
         L.check(L.load().hpfg_pack_weights(dev_tab.data_ptr(), d, 1, stream(device)), "pack")
 
-    def conv(self, a0, a1, N, H, W, stats=False, dgrad=False, math=0):
+    def conv(self, a0, a1, N, H, W, stats=False, dgrad=False, math=0, stat_acc=None, shards=1, bwd_stats=0, bwd_of=None):
+        """stat_acc / shards: with stats=True the BatchNorm sums ALSO go into this zeroed accumulator (HpfgConvArgs.stat_acc), next to the rows
+        of partial sums.  bwd_stats / bwd_of: the dgrad epilogue's backward sums (HpfgConvArgs.bwd_stats).  self.rows = rows the launch wrote."""
         lib = L.load()
         cout = self.cin if dgrad else self.cout
         cpad = self.cin_pad if dgrad else self.cout_pad
@@ -83,7 +85,13 @@ class AdHocConv:
         if stats:
             part = torch.zeros(lib.hpfg_conv_stat_blocks(N, H, W) * 2 * cpad, device=self.dev)   # unused rows stay 0
             ca.stat_partials = L.ptr(part)
+            if stat_acc is not None:
+                assert stat_acc.dtype == torch.int64 and stat_acc.numel() == shards * 2 * cpad * 2
+                ca.stat_acc, ca.stat_shards = L.ptr(stat_acc), shards
+        if bwd_stats:
+            ca.bwd_stats, ca.bwd_of = bwd_stats, bwd_of
         ca.out_pstride, ca.Cout, ca.CoutPad, ca.N, ca.H, ca.W, ca.taps = cout, cout, cpad, N, H, W, self.taps
+        self.rows = lib.hpfg_conv_stat_rows(C.byref(ca)) if stats else 0
         L.check(lib.hpfg_conv_fwd(C.byref(ca), stream(self.dev)), "conv_fwd")
         return out, part
 
@@ -112,3 +120,52 @@ def plain_act(t, C_, H, W):
         a.mode = L.ACT_STRIDED
         a.sn, a.sc, a.sy, a.sx = H * W * C_, 1, W * C_, C_
     return a
+
+
+# ---- BatchNorm sum accumulators (HpfgConvArgs.stat_acc / HpfgAct.bn_acc): long long [shard][which][C][limb] ---------------------------
+from fractions import Fraction
+
+ACC_SCALE = 2 ** 52      # a float t is added as hi + lo * 2^-52
+
+
+def acc_encode(t_f32):
+    """The two limbs hpfg_acc_add (csrc/common.h) adds for a float t, in numpy float32 like the device: r = rint(t), hi = r,
+    lo = rint((t - r) * 2^52).  -> (hi, lo) int64 arrays of t's shape."""
+    t = np.asarray(t_f32, dtype=np.float32)
+    r = np.rint(t)
+    lo = np.rint((t - r) * np.float32(ACC_SCALE))
+    assert r.dtype == np.float32 and lo.dtype == np.float32
+    return r.astype(np.int64), lo.astype(np.int64)
+
+
+def acc_totals(acc_tensor, C_, shards):
+    """Sum of an accumulator tensor over its shards as Python integers (no 64-bit wrap): object array [2 (which)][C][2 (limb)]."""
+    a = acc_tensor.detach().cpu().numpy().reshape(shards, 2, C_, 2).astype(object)
+    return a.sum(0)
+
+
+def acc_rows_totals(rows_f32):
+    """What acc_totals must give after one hpfg_acc_add per row of partial sums: rows [R][2][C] float32 -> object array [2][C][2]."""
+    hi, lo = acc_encode(rows_f32)
+    return np.stack([hi.astype(object).sum(0), lo.astype(object).sum(0)], -1)
+
+
+def acc_decode(totals):
+    """float64 [2][C]: the correctly rounded value hi + lo * 2^-52 of every (hi, lo) pair of acc_totals."""
+    t = np.asarray(totals, dtype=object)
+    out = np.empty(t.shape[:-1], dtype=np.float64)
+    for i in np.ndindex(*out.shape):
+        out[i] = float(Fraction(int(t[i][0])) + Fraction(int(t[i][1]), ACC_SCALE))
+    return out
+
+
+def acc_from_rows(rows_f32, shards, device=None):
+    """An accumulator tensor [shards][2][C][2] (int64) holding one hpfg_acc_add per row of rows [R][2][C] float32, row r in shard r % shards."""
+    rows = np.asarray(rows_f32, dtype=np.float32)
+    hi, lo = acc_encode(rows)
+    acc = np.zeros((shards,) + rows.shape[1:] + (2,), dtype=np.int64)
+    for r in range(rows.shape[0]):
+        acc[r % shards, ..., 0] += hi[r]
+        acc[r % shards, ..., 1] += lo[r]
+    t = torch.from_numpy(acc)
+    return t if device is None else t.to(device)

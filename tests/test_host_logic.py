@@ -263,3 +263,48 @@ def test_desc_table_sub_ranges_alias_the_host_array():
     descs[1].Cout = 32
     assert host[0].Cout == 32
     assert C.addressof(host) == C.addressof(descs) + sz
+
+
+def test_acc_encode_reproduces_the_exact_limb_split_of_hpfg_acc_add():
+    """tests/helpers.py::acc_encode, the numpy float32 restatement of hpfg_acc_add (csrc/common.h): t = hi + lo * 2^-52 holds EXACTLY for every
+    float with |t| >= 2^-29 (and for 0), rint breaks ties to even, |lo| <= 2^51; acc_totals / acc_decode / acc_from_rows agree with it."""
+    from fractions import Fraction
+    from tests.helpers import ACC_SCALE, acc_decode, acc_encode, acc_from_rows, acc_rows_totals, acc_totals
+    rng = np.random.RandomState(5)
+    mant = rng.uniform(1.0, 2.0, 4000)
+    expo = rng.randint(-29, 40, 4000)
+    sign = rng.choice([-1.0, 1.0], 4000)
+    ties = [0.5, -0.5, 1.5, 2.5, -1.5, -2.5, 3.5]
+    big = [2.0 ** 24, 2.0 ** 24 + 2, -(2.0 ** 24) - 2, 2.0 ** 30 + 128, 3.0 * 2.0 ** 40, -(2.0 ** 62)]
+    edge = [0.0, 2.0 ** -29, -(2.0 ** -29), 1.0, -1.0, 0.49999997, 0.50000006, 8388607.5, -8388607.5, 4194303.75]
+    t = np.concatenate([sign * mant * 2.0 ** expo, ties, big, edge]).astype(np.float32)
+    hi, lo = acc_encode(t)
+    assert hi.dtype == np.int64 and lo.dtype == np.int64
+    for tv, h, l in zip(t.tolist(), hi.tolist(), lo.tolist()):
+        assert Fraction(h) + Fraction(l, ACC_SCALE) == Fraction(tv), (tv, h, l)      # exact, not merely to fp64 rounding
+        assert abs(l) <= 2 ** 51, (tv, l)
+    np.testing.assert_array_equal(hi.astype(np.float64) + lo.astype(np.float64) * 2.0 ** -52, t.astype(np.float64))
+    got = {tv: (int(h), int(l)) for tv, h, l in zip(ties, *acc_encode(np.float32(ties)))}
+    assert got == {0.5: (0, 2 ** 51), -0.5: (0, -(2 ** 51)), 1.5: (2, -(2 ** 51)), 2.5: (2, 2 ** 51), -1.5: (-2, 2 ** 51), -2.5: (-2, -(2 ** 51)),
+                   3.5: (4, -(2 ** 51))}
+    h, l = acc_encode(np.float32([2.0 ** 24 + 2, 2.0 ** 30 + 128]))
+    assert h.tolist() == [2 ** 24 + 2, 2 ** 30 + 128] and l.tolist() == [0, 0]
+    # below 2^-29 the low limb drops bits (the documented limit of the split), never more than half a unit of 2^-52
+    tiny = np.float32(2.0 ** -30 * 1.2345)
+    h, l = acc_encode(tiny)
+    assert h == 0 and abs(Fraction(int(l), ACC_SCALE) - Fraction(float(tiny))) <= Fraction(1, 2 * ACC_SCALE)
+    # rows -> accumulator tensor -> totals -> float64: integer sums, independent of the shard count
+    rows = (rng.randn(21, 2, 5) * 300).astype(np.float32)
+    want = acc_rows_totals(rows)
+    exact = np.array([[sum(Fraction(float(v)) for v in rows[:, w, c]) for c in range(5)] for w in range(2)], dtype=object)
+    for shards in (1, 2, 8):
+        acc = acc_from_rows(rows, shards)
+        assert tuple(acc.shape) == (shards, 2, 5, 2) and acc.dtype == torch.int64
+        tot = acc_totals(acc, 5, shards)
+        assert (tot == want).all()
+        assert all(Fraction(int(tot[w, c, 0])) + Fraction(int(tot[w, c, 1]), ACC_SCALE) == exact[w, c] for w in range(2) for c in range(5))
+        np.testing.assert_array_equal(acc_decode(tot), np.array([[float(exact[w, c]) for c in range(5)] for w in range(2)]))
+    assert (acc_from_rows(rows, 8)[1:] != 0).any()      # more than one shard in use
+    # 2048 adds of the largest low limb stay inside an int64 word; the Python-integer totals do not wrap beyond it either
+    worst = torch.full((8, 2, 1, 2), 2048 * 2 ** 51, dtype=torch.int64)
+    assert int(acc_totals(worst, 1, 8)[0, 0, 1]) == 2 ** 65
