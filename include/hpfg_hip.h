@@ -365,8 +365,10 @@ typedef struct HpfgLossArgs {
   const float* cons_mask;   /* [N-n_lab][H][W] 0/1 weights of the consistency term, or NULL.  With a mask the term is
                                sum(mask * d^2) / (2*sum(mask) + 1e-16)  (UAMT, 2019_07...Uncertainty_Aware...py:160-164) instead of the mean */
 } HpfgLossArgs;
+/* A row of `partials` / `sums`: 0 nll0, 1 cnt0, 2 nll1, 3 cnt1, 4 mse, 5 sum mask, 6..7 unused, then 8 + g * 3 * S + k * S + c for label group g,
+   k = 0 / 1 / 2 = I (sum p t) / Z (sum p p) / Y (sum t t) and class c, with class stride S = 4 for C <= 4 and S = 16 above: 8 + 6 * S floats */
 #define HPFG_LOSS_NSUM 32           /* C <= 4 */
-#define HPFG_LOSS_NSUM_WIDE 104     /* 5 <= C <= 16: six scalars (+2 unused), then I0, Z0, Y0, I1, Z1, Y1 in blocks of 16 (csrc/loss_wide.hip) */
+#define HPFG_LOSS_NSUM_WIDE 104     /* 5 <= C <= 16 */
 int hpfg_loss_blocks(int N, int H, int W);
 int hpfg_loss_nsum(int C);          /* floats per row of `partials` and in `sums`: HPFG_LOSS_NSUM for C <= 4, HPFG_LOSS_NSUM_WIDE above */
 int hpfg_seg_loss_partials(const HpfgLossArgs* a, void* stream);   /* softmax + CE/Dice/MSE partial sums */

@@ -1,4 +1,4 @@
-"""GPU parity of the fused loss at 5..16 classes (the wide kernel family, csrc/loss_wide.hip) against the oracle, CPU autograd and the
+"""GPU parity of the fused loss at 5..16 classes (csrc/loss.hip; 104-float sums rows) against the oracle, CPU autograd and the
 reference's own nine-class outputs (tests/golden/losses_c9.npz, tools/make_golden_multiclass.py).  Bounds are those of
 tests/test_gpu_loss.py: 1e-5 on loss values, 1e-6 on the MSE, 1e-7 + 1e-4 * max|ref| on gradients.
 
@@ -167,7 +167,7 @@ def test_seventeen_classes_raise_value_error():
 
 
 def test_four_classes_unchanged(golden_dir):
-    """C = 4 still takes the narrow family: the composite of tests/test_gpu_loss.py on the reference fixture, value and gradient."""
+    """C = 4: the composite of tests/test_gpu_loss.py on the reference fixture, value and gradient."""
     d = np.load(f"{golden_dir}/losses.npz")
     logits = torch.from_numpy(d["logits"]).to(DEV)
     tl = torch.from_numpy(d["t_logits"]).to(DEV)

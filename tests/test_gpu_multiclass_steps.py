@@ -185,7 +185,7 @@ def test_captured_step_equals_eager_nine_classes(make):
     le, pe = _run(make, False, inputs)
     lg, pg = _run(make, True, inputs)
     assert torch.isfinite(le).all() and float(le.min()) > 0.0
-    assert torch.equal(le, lg), (le, lg)                          # the captured step replays the wide loss buffers: same bits as eager
+    assert torch.equal(le, lg), (le, lg)                          # the captured step replays the 104-float loss buffers: same bits as eager
     lg2, pg2 = _run(make, True, inputs)
     assert torch.equal(lg, lg2)
     assert all(torch.equal(a, b) for a, b in zip(pg, pg2))        # the captured run twice from the same state: bit-equal parameters

@@ -1,4 +1,4 @@
-"""GPU parity of the whole U-Net at 5, 9 and 16 classes (decoder.out_conv beyond four output channels, the wide loss family): every
+"""GPU parity of the whole U-Net at 5, 9 and 16 classes (decoder.out_conv beyond four output channels, the fused loss on 104-float sums rows): every
 parameter gradient against the CPU oracle under the ensemble control of tests/test_gpu_unet.py::test_backward_all_parameter_gradients,
 and the eval-mode logits within 1e-3."""
 import numpy as np

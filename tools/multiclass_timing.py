@@ -1,9 +1,11 @@
 """Timings of the 5..16-class range on one GPU (diagnostics; the benchmark driver has no line for it).
 
-  loss   the fused loss at 16 x 224 x 224 for C in {4, 8, 9, 16}: [partial sums + reduction + finalize] and [backward], with a teacher
-         (Mean-Teacher form: 8 labelled + 8 unlabelled images, MSE against teacher logits) and without (16 labelled images).  C = 4 runs the
-         narrow kernels (csrc/loss.hip), the yardstick; C > 4 the wide family (csrc/loss_wide.hip).  Each case is a captured hipGraph of
-         BLOCK launches; device-event time per replay, alternating over the cases, median over the rounds; algorithmic bytes / time.
+  loss   the fused loss (csrc/loss.hip, one kernel family) at 16 x 224 x 224 for C in {2, 4, 8, 9, 12, 16} -- both ends of the range, both
+         class strides of the sums layout, 16-byte and scalar accesses, an occupancy edge of the partial-sum kernel (8 -> 9 classes: 6 -> 5
+         waves per SIMD): [partial sums + reduction + finalize] and [backward], with a teacher (Mean-Teacher form: 8 labelled + 8 unlabelled
+         images, MSE against teacher logits) and without (16 labelled images).  C = 4 is the yardstick of the last column.  Each case is a
+         captured hipGraph of BLOCK launches; device-event time per replay, alternating over the cases, median over the rounds; algorithmic
+         bytes / time.
   step   ms per replayed (hipGraph) Mean-Teacher step at 8 + 8 images of 224 x 224 for 4, 8 and 9 classes in alternating blocks, and, from
          a second capture with device time stamps around the launches (engine.MarkLog), the launches of decoder.out_conv.
 
@@ -20,6 +22,7 @@ sys.path.insert(0, ROOT)
 
 N, HW = 16, 224
 ROUNDS, BLOCK = 9, 20
+LOSS_CLASSES = (2, 4, 8, 9, 12, 16)
 
 
 def _emit(out, lines):
@@ -77,7 +80,7 @@ def _loss_case(ncls, teacher):
 
 def loss(out):
     import torch
-    cases = [_loss_case(c, t) for t in (True, False) for c in (4, 8, 9, 16)]
+    cases = [_loss_case(c, t) for t in (True, False) for c in LOSS_CLASSES]
     res = {}
     for which in ("fwd", "bwd"):
         for c in cases:
@@ -96,17 +99,16 @@ def loss(out):
     lines = ["", f"== (a) fused loss kernels, {N} x {HW} x {HW}; {torch.cuda.get_device_name(0)}",
              f"   device-event time per launch: hipGraph of {BLOCK} launches, median (min .. max) of {ROUNDS} alternating replays",
              "   fwd = partial sums + reduction + finalize, bwd = dlogits; bytes = logits (+ teacher logits of the unlabelled half) + labels (+ dlogits)",
-             "   C = 4: narrow family (loss.hip), the yardstick; C = 8, 16: wide family, 16-byte accesses; C = 9: wide family, scalar accesses",
+             "   C = 4: the yardstick; C % 4 == 0: 16-byte accesses, other C: scalar accesses; C <= 4: 32-float sums rows, above: 104-float rows",
              f"   {'form':>10} {'C':>3} {'call':>4} | {'us':>28} | {'MB':>7} | {'GB/s':>7} | vs C = 4"]
     for teacher in (True, False):
         for which in ("fwd", "bwd"):
-            base = None
-            for ncls in (4, 8, 9, 16):
-                v = res[(ncls, teacher, which)]
-                b = next(c for c in cases if c["C"] == ncls and c["teacher"] == teacher)["bytes"][which]
+            nbytes = {c["C"]: c["bytes"][which] for c in cases if c["teacher"] == teacher}
+            base = nbytes[4] / statistics.median(res[(4, teacher, which)]) / 1e3
+            for ncls in LOSS_CLASSES:
+                v, b = res[(ncls, teacher, which)], nbytes[ncls]
                 med = statistics.median(v)
                 rate = b / med / 1e3
-                base = rate if ncls == 4 else base
                 lines.append(f"   {'teacher' if teacher else 'no teacher':>10} {ncls:3d} {which:>4} | {med:9.2f} ({min(v):.2f} .. {max(v):.2f}){'':>3} | {b / 1e6:7.2f} | "
                              f"{rate:7.1f} | {rate / base:.2f}")
     _emit(out, lines)
