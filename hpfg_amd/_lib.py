@@ -15,11 +15,11 @@ LIB_PATH = os.path.join(_HERE, "lib", "libhpfg_hip.so")
 # enums from include/hpfg_hip.h
 BN_MEAN, BN_RSTD, BN_SCALE, BN_SHIFT, BN_K1, BN_K2, BN_K3, BN_SPARE, BN_ROWS = range(9)
 ACT_NONE, ACT_PLAIN, ACT_STRIDED, ACT_BNACT, ACT_BNACT_POOL, ACT_UP2X, ACT_DZ, ACT_SPLIT16, ACT_UPBWD = range(9)
-OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP = 0, 1, 2, 3          # hpfg_set_option
+OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP, OPT_UPDATE_PACK = 0, 1, 2, 3, 4        # hpfg_set_option
 LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
 LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 139
+VERSION = 140
 RESIZE_TAPS = 36            # HPFG_RESIZE_TAPS: coefficients per output sample and axis of hpfg_resize_cubic's tap tables
 SURFACE_SEGS = 32           # HPFG_SURFACE_SEGS: surface-point segments of hpfg_surface_*, (class - 1) * 2 + side (0 = pred, 1 = gt)
 MATH_F32, MATH_BF16X3 = 0, 1
@@ -94,6 +94,12 @@ class PackDesc(C.Structure):
                 ("CoutPad", C.c_int32), ("CinPad", C.c_int32), ("taps", C.c_int32), ("kc", C.c_int32)]
 
 
+class UpdatePackDesc(C.Structure):
+    _fields_ = [("w_off", C.c_long), ("b_off", C.c_long), ("wpk16_fwd", C.c_void_p), ("wpk16_dgrad", C.c_void_p), ("bias_pad", C.c_void_p),
+                ("t_wpk16_fwd", C.c_void_p), ("t_bias_pad", C.c_void_p), ("Cout", C.c_int32), ("Cin", C.c_int32), ("CoutPad", C.c_int32),
+                ("CinPad", C.c_int32), ("taps", C.c_int32), ("kc", C.c_int32), ("kc_t", C.c_int32), ("reserved", C.c_int32)]
+
+
 class LossArgs(C.Structure):
     _fields_ = [("logits", C.c_void_p), ("t_logits", C.c_void_p), ("labels0", C.c_void_p), ("labels1", C.c_void_p),
                 ("coef", C.c_void_p), ("partials", C.c_void_p), ("sums", C.c_void_p), ("out", C.c_void_p),
@@ -113,6 +119,8 @@ PROTOTYPES = {
     "hpfg_version": (_i, []),
     "hpfg_last_error": (C.c_char_p, []),
     "hpfg_set_option": (_i, [_i, _i]),
+    "hpfg_get_option": (_i, [_i]),
+    "hpfg_conv3x3_first_fwd_bump": (_i, [C.POINTER(Act), _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "hpfg_conv3x3_first_fwd": (_i, [C.POINTER(Act), _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "hpfg_conv_fwd": (_i, [C.POINTER(ConvArgs), _p]),
     "hpfg_conv_stat_blocks": (_i, [_i, _i, _i]),
@@ -209,6 +217,7 @@ PROTOTYPES = {
     "hpfg_adamw_step": (_i, [_p, _p, _p, _p, _l, _p, _p, _f, _f, _f, _f, _f, _p]),
     "hpfg_ema_update": (_i, [_p, _p, _l, _p, _p]),
     "hpfg_sgd_ema_step": (_i, [_p, _p, _p, _l, _p, _f, _f, _f, _p, _l, _p, _p]),
+    "hpfg_sgd_ema_pack_step": (_i, [_p, _p, _p, _l, _p, _f, _f, _f, _p, _l, _p, _p, C.POINTER(UpdatePackDesc), _i, _p, C.POINTER(C.c_long), _i, _p]),
     "hpfg_attn_mfma_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "hpfg_attn_mfma_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "hpfg_attn_mfma_blocks": (_i, [_i]),
@@ -275,6 +284,8 @@ def load() -> C.CDLL:
             lib.hpfg_set_option(OPT_FIRST_WGRAD, 0)
         if os.environ.get("HPFG_NARROW_DEEP") is not None:      # A/B runs: workgroup threshold below which a 3x3 launch takes 32-wide slices (0: never)
             lib.hpfg_set_option(OPT_NARROW_DEEP, int(os.environ["HPFG_NARROW_DEEP"]))
+        if os.environ.get("HPFG_UPDATE_PACK", "1") == "0":      # A/B runs: every forward packs its own weight fragments
+            lib.hpfg_set_option(OPT_UPDATE_PACK, 0)
         _lib = lib
     return _lib
 

@@ -25,7 +25,20 @@ struct HpfgFirstConvArgs {   // kernel argument of the first-layer kernels
   float* stat_partials; // or NULL
   long long* stat_acc;  // or NULL: the sums go into the layer accumulator by integer atomics instead (HpfgConvArgs.stat_acc)
   int stat_shards;
+  // the per-forward counters of hpfg_pack_weights_bump, for a forward that starts without that launch (hpfg_conv3x3_first_fwd_bump)
+  long long* counters;  // or NULL
+  int n_counters;
+  int* seed_word;       // or NULL
+  int seed_add;
 };
+
+// workgroup 0, before anything else: num_batches_tracked += 1, seed word += seed_add (the values pack_weights_kernel would have left)
+__device__ __forceinline__ void first_bump(const HpfgFirstConvArgs& q) {
+  if (blockIdx.x == 0) {
+    for (int i = threadIdx.x; i < q.n_counters; i += 256) q.counters[i] += 1;
+    if (threadIdx.x == 0 && q.seed_word && q.seed_add) *q.seed_word = (*q.seed_word + q.seed_add) & 0x7FFFFFFF;
+  }
+}
 
 inline bool tile_is_big(int H, int W) { return (H % 16 == 0) && (W % 16 == 0); }
 
@@ -46,6 +59,7 @@ __global__ __launch_bounds__(256) HPFG_NO_PK_F32 void conv_first_kernel(HpfgFirs
   __shared__ float red[2][4][CO];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = tiles_x * tiles_y, nwork = ntiles * N;
+  first_bump(q);
   for (int i = tid; i < 9 * Cin * CO; i += 256) {   // wl[(tap*Cin+ci)*16+co] = w[co][ci][tap]
     int co = i % CO, r = i / CO, ci = r % Cin, tap = r / Cin;
     wl[i] = w[(co * Cin + ci) * 9 + tap];
@@ -135,7 +149,8 @@ __global__ __launch_bounds__(256) void conv_first_mfma_kernel(HpfgFirstConvArgs 
   __shared__ float red[2][4][CO];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntiles = tiles_x * tiles_y, nwork = ntiles * N;
-  const int co_a = lane & 15, kq = lane >> 4;                 // A: row = output channel, k-local = lane >> 4; B: column = pixel, k-local = lane >> 4
+  first_bump(q);
+  const int co_a = lane & 15, kq = lane >> 4;                // A: row = output channel, k-local = lane >> 4; B: column = pixel, k-local = lane >> 4
   // k = ci * 9 + tap, ascending: the order of the VALU loop (for ci: for tap), so the fmaf chain of the MFMA reproduces its sums
   float wa[KS];
   int boff[KS];
@@ -367,7 +382,18 @@ static int conv_first_impl(const HpfgFirstConvArgs* q, int N, int H, int W, int 
 extern "C" int hpfg_conv3x3_first_fwd(const HpfgAct* x, const float* w_oihw, const float* bias, float* out, float* stat_partials,
                                       int N, int H, int W, int Cin, int Cout, void* stream) {
   HPFG_ARG_CHECK(x, "conv_first: null pointer");
-  HpfgFirstConvArgs a = {*x, w_oihw, bias, out, stat_partials, nullptr, 1};
+  HpfgFirstConvArgs a = {*x, w_oihw, bias, out, stat_partials, nullptr, 1, nullptr, 0, nullptr, 0};
+  return conv_first_impl(&a, N, H, W, Cin, Cout, stream);
+}
+
+extern "C" int hpfg_conv3x3_first_fwd_bump(const HpfgAct* x, const float* w_oihw, const float* bias, float* out, float* stat_partials, long long* stat_acc,
+                                           int stat_shards, long long* counters, int n_counters, int32_t* seed_word, int seed_add, int N, int H, int W,
+                                           int Cin, int Cout, void* stream) {
+  HPFG_ARG_CHECK(x, "conv_first_bump: null pointer");
+  HPFG_ARG_CHECK(!stat_acc || (stat_shards >= 1 && stat_shards <= HPFG_ACC_MAX_SHARDS && (stat_shards & (stat_shards - 1)) == 0),
+                 "conv_first_bump: bad shard count %d", stat_shards);
+  HPFG_ARG_CHECK(n_counters >= 0 && (n_counters == 0 || counters) && (seed_add == 0 || seed_word), "conv_first_bump: bad counter arguments");
+  HpfgFirstConvArgs a = {*x, w_oihw, bias, out, stat_partials, stat_acc, stat_acc ? stat_shards : 1, counters, n_counters, seed_word, seed_add};
   return conv_first_impl(&a, N, H, W, Cin, Cout, stream);
 }
 
@@ -375,7 +401,7 @@ extern "C" int hpfg_conv3x3_first_fwd_acc(const HpfgAct* x, const float* w_oihw,
                                           int stat_shards, int N, int H, int W, int Cin, int Cout, void* stream) {
   HPFG_ARG_CHECK(x && stat_acc, "conv_first_acc: null pointer");
   HPFG_ARG_CHECK(stat_shards >= 1 && stat_shards <= HPFG_ACC_MAX_SHARDS && (stat_shards & (stat_shards - 1)) == 0, "conv_first_acc: bad shard count %d", stat_shards);
-  HpfgFirstConvArgs a = {*x, w_oihw, bias, out, stat_partials, stat_acc, stat_shards};
+  HpfgFirstConvArgs a = {*x, w_oihw, bias, out, stat_partials, stat_acc, stat_shards, nullptr, 0, nullptr, 0};
   return conv_first_impl(&a, N, H, W, Cin, Cout, stream);
 }
 

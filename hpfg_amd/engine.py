@@ -180,6 +180,13 @@ class UNetEngine:
         self.wpk16_d = {s.name: torch.empty(self.lib.hpfg_wpk16_elems(s.cout, s.cin_pad, s.taps, self.kc[s.name]), dtype=torch.bfloat16, device=device)
                         for s in self.packed}
         self._pack_tables: Dict[tuple, DescTable] = {}   # (math, with_dgrad) -> descriptors, built on first use
+        # Fragments the optimizer's update launch wrote (hpfg_sgd_ema_pack_step, utils/optim.py) are CURRENT: the next forward starts without a
+        # pack launch.  frag_token: what the owner's weights looked like to the host when they were written (UNet._weights_token), None = stale;
+        # the model compares it in front of every forward and says so in frag_ok.  Anything else that writes weights leaves them stale.
+        self.frag_token, self.frag_dgrad, self.frag_ok = None, False, False
+        self.pads_zeroed: set = set()      # "f" / "d": a full bf16x3 pack has written that layout once, padding included (the update launch writes weights only)
+        self.last_fwd_packed = True
+        self._first_bump: Optional[tuple] = None      # (counters, seed_add) for the first conv of a forward that does not pack
         # BatchNorm sums through integer atomics (csrc/common.h: hpfg_acc_add): a conv adds its per-channel sums to the layer's accumulator and
         # every forward consumer derives scale / shift from it in its prologue, so NO finalize launch sits between two convs; ONE launch at the
         # end of the forward (hpfg_bn_acc_finalize) writes all 18 tables for the backward kernels and the running statistics.  bf16x3 kernels,
@@ -401,6 +408,8 @@ class UNetEngine:
             assert counters.dtype == torch.int64 and counters.is_contiguous() and counters.device == self.dev
         self._call(self.lib.hpfg_pack_weights_bump, dev, host, n, L.ptr(counters), counters.numel() if counters is not None else 0, L.ptr(self.seed_dev), int(seed_add),
                    None, 0, tag="pack_weights")
+        if self._b16:
+            self.pads_zeroed |= {"f", "d"} if with_dgrad else {"f"}
 
     def _finalize_bwd_all(self, lo: int, hi: int):
         """hpfg_bn_acc_bwd_finalize for BatchNorm layers [lo, hi) of self.bn_layers (encoder layers come first): dgamma / dbeta (+ the k rows)
@@ -489,7 +498,14 @@ class UNetEngine:
                 self.acc_all.zero_()
             self._acc_dirty = True
         pack_args = dict(with_dgrad=bool(train and needs_grad), counters=counters, seed_add=1 if seed_step == SEED_BUMP else 0)
-        if not (self.pack_overlap and train):
+        self._first_bump = None
+        self.last_fwd_packed = not (self._b16 and self.frag_ok and self.frag_token is not None and (self.frag_dgrad or not pack_args["with_dgrad"]))
+        self.frag_ok = False
+        if not self.last_fwd_packed:      # current fragments: no pack launch (and no fork for it); the two counters ride in the first conv
+            if counters is not None or pack_args["seed_add"]:
+                self._first_bump = (counters, pack_args["seed_add"])
+            pack_args = None
+        elif not (self.pack_overlap and train):
             self.pack(**pack_args)
             pack_args = None
         if self.marks is not None:
@@ -506,7 +522,12 @@ class UNetEngine:
         if s.idx == 0:
             a0, _ = self.input_acts(s.name)
             w, b = L.ptr(self.params[f"{s.name}.weight"]), L.ptr(self.params[f"{s.name}.bias"])
-            if acc:
+            if self._first_bump is not None:
+                (cnt, seed_add), self._first_bump = self._first_bump, None
+                self._call(self.lib.hpfg_conv3x3_first_fwd_bump, C.byref(a0), w, b, L.ptr(out), None if acc or not want_stats else L.ptr(self.partials),
+                           L.ptr(self.acc_of[s.name]) if acc else None, self.acc_shards[s.name], L.ptr(cnt), cnt.numel() if cnt is not None else 0,
+                           L.ptr(self.seed_dev), int(seed_add), self.N, s.h, s.w, s.cin, s.cout, tag="fwd:" + s.name)
+            elif acc:
                 self._call(self.lib.hpfg_conv3x3_first_fwd_acc, C.byref(a0), w, b, L.ptr(out), None, L.ptr(self.acc_of[s.name]), self.acc_shards[s.name],
                            self.N, s.h, s.w, s.cin, s.cout, tag="fwd:" + s.name)
             else:

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 import os
+import weakref
 
 from .. import _lib as L
 from .. import engine as E
@@ -77,12 +78,34 @@ def _neck(cin: int, hid: int, out: int = 128) -> nn.Module:
     return m
 
 
+class _WatchedParameter(nn.Parameter):
+    """A U-Net parameter after UNet._flatten (same object, class changed in place).  ``p.data`` hands out a tensor with a version counter of
+    its own, so an in-place write through it (``p.data.mul_(0.5)``, the reference's EMA idiom) is invisible to UNet._weights_token: the
+    access itself marks the owner's weight fragments stale.  Pickles as a plain nn.Parameter."""
+
+    @property
+    def data(self):
+        owner = self.__dict__.get("_hpfg_owner")
+        net = owner() if owner is not None else None
+        if net is not None:
+            net.mark_fragments_stale()
+        return torch.Tensor.data.__get__(self)
+
+    @data.setter
+    def data(self, value):
+        torch.Tensor.data.__set__(self, value)
+
+    def __reduce_ex__(self, proto):
+        return nn.Parameter(torch.Tensor.data.__get__(self), self.requires_grad).__reduce_ex__(proto)
+
+
 class _UNetFn(torch.autograd.Function):
     """Whole-network autograd node: forward = engine.forward, backward = engine.backward into the flat gradient buffer."""
 
     @staticmethod
     def forward(ctx, anchor: torch.Tensor, x: torch.Tensor, net: "UNet", want_feat: bool, needs_grad: bool):
         eng = net._acquire_engine(x)
+        net._last_engine = eng      # (the optimizer's update launch writes the next step's weight fragments for this one: utils/optim.py)
         if getattr(net, "_bn_bump_pending", False):
             eng.bump_counters, net._bn_bump_pending = net._flat_long, False
         # (an eval-mode forward draws no masks: it must not consume a seed either, or an evaluation between two training iterations would shift
@@ -168,6 +191,10 @@ class UNet(nn.Module):
                 k = p.numel()
                 p.data = flat[off:off + k].view(p.shape)
                 p.grad = None
+                if type(p) is nn.Parameter:
+                    p.__class__ = _WatchedParameter
+                if isinstance(p, _WatchedParameter):
+                    p.__dict__["_hpfg_owner"] = weakref.ref(self)
                 self._offsets[n] = (off, k)
                 off += k
             bs = self._float_buffers()
@@ -182,7 +209,7 @@ class UNet(nn.Module):
             for i, (n, b) in enumerate(ls):
                 b.data = fl[i]
         self._flat, self._flat_grad, self._flat_buf, self._flat_long = flat, flat_grad, fb, fl
-        self._engines = {}
+        self._engines, self._last_engine = {}, None
         self._anchor = torch.zeros(1, device=dev, requires_grad=True)
         self._backbone_numel = sum(p.numel() for n, p in ps if n.startswith("encoder.") or n.startswith("decoder."))
         self._encoder_numel = sum(p.numel() for n, p in ps if n.startswith("encoder."))
@@ -210,7 +237,7 @@ class UNet(nn.Module):
         nn.Module.__init__(new)
         import copy
         for k, v in self.__dict__.items():
-            if k in ("_flat", "_flat_grad", "_flat_buf", "_flat_long", "_engines", "_anchor", "dp"):
+            if k in ("_flat", "_flat_grad", "_flat_buf", "_flat_long", "_engines", "_last_engine", "_anchor", "dp"):
                 continue
             new.__dict__[k] = copy.deepcopy(v, memo)
         new.dp = self.dp
@@ -223,7 +250,21 @@ class UNet(nn.Module):
     def load_state_dict(self, *a, **k):
         out = super().load_state_dict(*a, **k)
         self._ensure_flat()
+        self.mark_fragments_stale()
         return out
+
+    # ---- weight fragments written by the optimizer's update launch (UNetEngine.frag_token) --------------------------------
+    def _weights_token(self) -> tuple:
+        """What the host can see of the weights' state: the math mode and torch's version counters of the flat buffer and of every parameter
+        (any torch in-place write through either advances one of them).  Writes through raw pointers -- the library's own update launches --
+        say so themselves (mark_fragments_stale)."""
+        return (self.math, self._flat.data_ptr(), self._flat._version, sum(p._version for p in self.parameters()))
+
+    def mark_fragments_stale(self):
+        """Something wrote the weights: every engine packs again at the start of its next forward."""
+        for pool in self.__dict__.get("_engines", {}).values():
+            for e in pool:
+                e.frag_token = None
 
     @property
     def flat_params(self) -> torch.Tensor:
@@ -304,6 +345,9 @@ class UNet(nn.Module):
         rank = self.dp.rank if self.dp is not None else 0
         eng.base_seed = (self.dropout_seed + 0x632BE5AB * rank) & 0x7FFFFFFF      # every data-parallel rank draws its own masks too
         eng.math = L.MATH_BF16X3 if self.math == "bf16x3" else L.MATH_F32
+        if eng.frag_token is not None and eng.frag_token != self._weights_token():
+            eng.frag_token = None
+        eng.frag_ok = eng.frag_token is not None
         eng.defer_wgrad = bool(getattr(self, "defer_wgrad", False))
         eng.pack_overlap = bool(getattr(self, "_alone", False))
         eng.after_layer = getattr(self, "_after_layer", None)

@@ -340,7 +340,7 @@ class _TeacherStudentStep(_StepBase):
         (2017_03_NIPS_Mean-Teacher_ACDC.py:108-113) -- as ONE launch over the student's flat buffers where the optimizer offers it."""
         fs, ft = getattr(self.model, "flat_params", None), getattr(self.ema_model, "flat_params", None)
         if isinstance(self.optimizer, FusedSGD) and fs is not None and ft is not None and fs.numel() == ft.numel() and fs.is_cuda:
-            self.optimizer.step(push_lr=False, ema=(ft, fs.numel(), self.sc.view(S_ALPHA)))
+            self.optimizer.step(push_lr=False, ema=(ft, fs.numel(), self.sc.view(S_ALPHA), self.ema_model))
         else:
             self.optimizer.step(push_lr=False)
             update_ema_variables(self.model, self.ema_model, self.args.ema_decay, 0, alpha_dev=self.sc.view(S_ALPHA))
@@ -579,6 +579,10 @@ class HPFGStep(_StepBase):
             model1.skip_necks = True
             if isinstance(self.optimizer1, (FusedSGD, FusedAdamW)):
                 self.optimizer1.active_numel = model1.backbone_numel()
+        if isinstance(self.optimizer2, FusedSGD):
+            # the backbone EMA overwrites the second student's conv weights right behind its optimizer step (device_update): fragments written
+            # by that step would be stale before any forward read them
+            self.optimizer2.pack_fragments = False
         self.dense_loss = Dense_Loss(args.batch_size + args.unlabel_batch_size, self.dev)
         self.dense_loss.dp = dp      # global-batch mode: NT-Xent over the gathered features of all ranks (main.py:172 contrasts the whole batch)
         self.mask_generator = BoxMaskGenerator(prop_range=(0.25, 0.5), n_boxes=4, random_aspect_ratio=True, prop_by_area=True,
@@ -746,8 +750,13 @@ class GraphedStep:
             raise GraphNotCapturable(f"GraphedStep: {type(step_obj).__name__} has no device_fwd_bwd / exchange / device_update split, so its gradient "
                                "exchange would be captured into the graph; run it eager under data parallel")
         self._freeze_seed_updates(True)
+        engines = [(m, e) for m in self.s.models for pool in getattr(m, "_engines", {}).values() for e in pool]
+        for _, e in engines:
+            e.last_fwd_packed = True
+        self._nopack = []
         try:
             self._capture(dp, mode_split=self.split)
+            self._nopack = [(m, e) for m, e in engines if not e.last_fwd_packed]      # forwards captured without a pack launch (_repack_stale)
         finally:          # whatever a capture raises, the networks leave graph-seed mode and no bucket hook stays installed
             self._freeze_seed_updates(False)
             if dp is not None:
@@ -815,6 +824,15 @@ class GraphedStep:
             else:
                 m._fwds_per_replay = getattr(m, "_graph_fwds", 0)      # (UNet.bump_graph_seed keeps the host's seed counter in step with the replays)
 
+    def _repack_stale(self):
+        """The capture froze, per engine, the decision not to pack: the forward of an engine whose fragments were current (written by the
+        update launch of the step before) has no pack launch in the graph.  If something wrote the weights since -- load_state_dict, an
+        in-place torch op, an update outside this graph -- pack eagerly in front of the replay; the replayed update keeps them current after."""
+        for m, e in self._nopack:
+            if e.frag_token is None or e.frag_token != m._weights_token():
+                e.pack(with_dgrad=e.frag_dgrad)
+                e.frag_token = m._weights_token()
+
     def step(self, inputs, cur_itrs, **kw):
         for dst, src in zip(self.static, inputs):
             if dst is not src:
@@ -823,6 +841,7 @@ class GraphedStep:
         self.s.sc.push()          # eager H2D copy of this step's scalars from a fresh ring slot, ordered in front of the replay
         for m in self.s.models:
             m.bump_graph_seed()      # (the U-Nets advance their seed words inside the captured forward; the SegFormer branch does it here)
+        self._repack_stale()
         if self.split:
             dp = self.s.dp
             for i, g in enumerate(self.graphs):

@@ -7,6 +7,8 @@ It is a ``torch.optim.Optimizer`` (param_groups, state_dict, zero_grad), so the 
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from .. import _lib as L
@@ -26,6 +28,8 @@ class FusedSGD(torch.optim.Optimizer):
         # torch.optim.SGD skips a parameter whose .grad is None (no weight decay, no momentum).  A step that never back-propagates into a
         # trailing part of the flat buffer (HPFG's first student: its projection necks' outputs are discarded, main.py:152) says so here.
         self.active_numel = None
+        self.pack_fragments = True      # False: a step whose next launch overwrites this model's weights anyway (HPFG's second student) says so
+        self._pack_plan = None      # descriptors of the update launch that also writes the weight fragments (_update_pack_plan)
 
     def zero_grad(self, set_to_none: bool = False):
         if hasattr(self.model, "_hpfg_generic_flat"):      # a module laid out by flatten_parameters (SegFormer_Plus): see FusedAdamW.zero_grad
@@ -40,10 +44,59 @@ class FusedSGD(torch.optim.Optimizer):
         self._lr_host[0] = float(self.param_groups[0]["lr"])
         self._lr_dev.copy_(self._lr_host, non_blocking=True)
 
+    def _update_pack_plan(self, n_sgd: int, teacher, n_ema: int):
+        """Descriptor table of hpfg_sgd_ema_pack_step for the engine that ran the model's last forward (and the teacher's), or None where the
+        launch does not apply: not an hpfg_amd U-Net in bf16x3 math, a conv layer outside the updated range, or fragment buffers whose padding
+        no pack launch has zeroed yet (a fresh engine packs once by itself).  Returns (plan, student engine, teacher engine or None)."""
+        from ..engine import DescTable
+        m = self.model
+        eng = getattr(m, "_last_engine", None)
+        if eng is None or getattr(m, "math", None) != "bf16x3" or eng.math != L.MATH_BF16X3 or not {"f", "d"} <= eng.pads_zeroed:
+            return None
+        if not any(eng is e for pool in m._engines.values() for e in pool):      # (the model was re-flattened: its engines are gone)
+            return None
+        layers = sorted(eng.packed, key=lambda s: m._offsets[f"{s.name}.weight"][0])
+        end = max(sum(m._offsets[f"{s.name}.bias"]) for s in layers)
+        teng = getattr(teacher, "_last_engine", None) if teacher is not None else None
+        # the teacher rides along with all of its layers or not at all: same layout, every conv inside the averaged slice, padding zeroed
+        if teng is not None and (teacher.math != "bf16x3" or teng.math != L.MATH_BF16X3 or "f" not in teng.pads_zeroed or end > n_ema
+                                 or teacher._offsets != m._offsets or not any(teng is e for pool in teacher._engines.values() for e in pool)):
+            teng = None
+        key = (eng, teng, m._flat.data_ptr(), n_sgd, n_ema)
+        if self._pack_plan is not None and self._pack_plan[0][0] is eng and self._pack_plan[0][1] is teng and self._pack_plan[0][2:] == key[2:]:
+            return self._pack_plan[1], eng, teng
+        if torch.cuda.is_current_stream_capturing():      # (the tables are copied to the device when they are built: not inside a capture)
+            return None
+        descs =(L.UpdatePackDesc * len(layers))()
+        gaps, at = [], 0
+        for d, s in zip(descs, layers):
+            (wo, wn), (bo, bn) = m._offsets[f"{s.name}.weight"], m._offsets[f"{s.name}.bias"]
+            if not (at <= wo and wo + wn <= bo and bo + bn <= n_sgd):
+                return None
+            d.w_off, d.b_off = wo, bo
+            d.wpk16_fwd, d.wpk16_dgrad, d.bias_pad = L.ptr(eng.wpk16_f[s.name]), L.ptr(eng.wpk16_d[s.name]), L.ptr(eng.bias_pad[s.name])
+            if teng is not None:
+                d.t_wpk16_fwd, d.t_bias_pad = L.ptr(teng.wpk16_f[s.name]), L.ptr(teng.bias_pad[s.name])
+            d.Cout, d.Cin, d.CoutPad, d.CinPad, d.taps = s.cout, s.cin, s.cout_pad, s.cin_pad, s.taps
+            d.kc, d.kc_t = eng.kc[s.name], (teng or eng).kc[s.name]
+            for lo, hi in ((at, wo), (wo + wn, bo)):
+                if hi > lo:
+                    gaps.append((lo, hi))
+            at = bo + bn
+        if at < n_sgd:
+            gaps.append((at, n_sgd))
+        gh = (C.c_long * (2 * max(len(gaps), 1)))(*[v for g_ in gaps for v in g_])
+        gd = torch.tensor([v for g_ in gaps for v in g_] or [0, 0], dtype=torch.int64).to(m._flat.device)
+        plan = (DescTable(descs, m._flat.device), gh, gd, len(gaps))
+        self._pack_plan = (key, plan)
+        return plan, eng, teng
+
     @torch.no_grad()
     def step(self, closure=None, push_lr: bool = True, ema=None):
-        """ema: optional (teacher_flat, numel, alpha_dev) -- the EMA teacher update of the same iteration rides along in the same launch
-        (hpfg_sgd_ema_step; bit-identical to step() followed by utils.update_ema_variables)."""
+        """ema: optional (teacher_flat, numel, alpha_dev[, teacher model]) -- the EMA teacher update of the same iteration rides along in the
+        same launch (hpfg_sgd_ema_step; bit-identical to step() followed by utils.update_ema_variables).  On an hpfg_amd U-Net in bf16x3 math
+        the launch also writes the weight fragments the next forward reads (hpfg_sgd_ema_pack_step: same update, bit for bit), for the engine
+        of the model's last forward and -- with the teacher model given -- the teacher's; every other engine of either model goes stale."""
         g = self.param_groups[0]
         if hasattr(self.model, "_hpfg_generic_flat"):
             gather_flat_grads(self.model, self.active_numel)
@@ -54,9 +107,28 @@ class FusedSGD(torch.optim.Optimizer):
             self.push_lr()
         st = torch.cuda.current_stream(flat.device).cuda_stream
         n_sgd = flat.numel() if self.active_numel is None else int(self.active_numel)
+        lib = L.load()
+        teacher = ema[3] if ema is not None and len(ema) > 3 else None
+        for m in (self.model, teacher):      # raw-pointer writes: torch's version counters do not see them
+            if hasattr(m, "mark_fragments_stale"):
+                m.mark_fragments_stale()
         if ema is not None:
-            t, n_ema, alpha_dev = ema
-            assert t.is_cuda and t.dtype == torch.float32 and t.numel() == flat.numel() and 0 <= n_ema <= n_sgd
+            assert ema[0].is_cuda and ema[0].dtype == torch.float32 and ema[0].numel() == flat.numel() and 0 <= ema[1] <= n_sgd
+        found = self._update_pack_plan(n_sgd, teacher, int(ema[1]) if ema is not None else 0) if (
+            self.pack_fragments and lib.hpfg_get_option(L.OPT_UPDATE_PACK) != 0 and hasattr(self.model, "_engines")) else None
+        if found is not None:
+            (table, gaps_host, gaps_dev, ngaps), eng, teng = found
+            dev, host, nl = table.sub(0, len(table.host))
+            t, n_ema, alpha_dev = (ema[0], int(ema[1]), ema[2]) if ema is not None else (None, 0, None)
+            L.check(lib.hpfg_sgd_ema_pack_step(L.ptr(flat), L.ptr(grad), L.ptr(self._mom), n_sgd, L.ptr(self._lr_dev), float(g["momentum"]),
+                                               float(g["weight_decay"]), float(self.grad_scale), L.ptr(t), n_ema, L.ptr(alpha_dev), dev, host, nl,
+                                               L.ptr(gaps_dev), gaps_host, ngaps, st), "sgd_ema_pack_step")
+            eng.frag_token, eng.frag_dgrad = self.model._weights_token(), True
+            if teng is not None:
+                teng.frag_token, teng.frag_dgrad = teacher._weights_token(), False
+            return
+        if ema is not None:
+            t, n_ema, alpha_dev = ema[:3]
             L.check(L.load().hpfg_sgd_ema_step(L.ptr(flat), L.ptr(grad), L.ptr(self._mom), n_sgd, L.ptr(self._lr_dev), float(g["momentum"]),
                                                float(g["weight_decay"]), float(self.grad_scale), L.ptr(t), int(n_ema), L.ptr(alpha_dev), st),
                     "sgd_ema_step")
@@ -167,6 +239,8 @@ class FusedAdamW(torch.optim.Optimizer):
         L.check(L.load().hpfg_adamw_step(L.ptr(flat), L.ptr(grad), L.ptr(self._m), L.ptr(self._v), n, L.ptr(self._lr_dev), L.ptr(self._step_dev),
                                          float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale), st),
                 "adamw_step")
+        if hasattr(self.model, "mark_fragments_stale"):      # a write through raw pointers (FusedSGD.step)
+            self.model.mark_fragments_stale()
 
     def state_dict(self):
         """torch's dict plus the flat Adam moments and the device step count (resuming must not reset them; the reference saves

@@ -109,6 +109,8 @@ def update_ema_variables(model, ema_model, alpha, global_step, alpha_dev: torch.
     n = src.numel() if numel is None else numel
     a = alpha_dev if alpha_dev is not None else _alpha_dev(src.device, ema_alpha(global_step, alpha))
     L.check(L.load().hpfg_ema_update(L.ptr(dst), L.ptr(src), n, L.ptr(a), torch.cuda.current_stream(src.device).cuda_stream), "ema_update")
+    if hasattr(ema_model, "mark_fragments_stale"):      # a write through raw pointers: the target's engines pack again (UNetEngine.frag_token)
+        ema_model.mark_fragments_stale()
 
 
 def update_ema_variables_backbone(model, ema_model, alpha, global_step, alpha_dev: torch.Tensor = None):

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 139
+#define HPFG_VERSION 140
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -177,8 +177,10 @@ const char* hpfg_last_error(void);
  * HPFG_OPT_FIRST_MFMA: 0 = the 1- / 3-channel first layer as a VALU loop instead of the MFMA form (bit-identical outputs);
  * HPFG_OPT_FIRST_WGRAD: 0 = the first layer's weight gradient on the tile kernel of hpfg_fused_bwd instead of the streaming kernel;
  * HPFG_OPT_NARROW_DEEP: the workgroup count up to which a 3x3 launch on 4 x 16-pixel tiles takes 32-wide instead of 64-wide output-channel slices
- *   (default 128: launches that would leave half of the CUs idle; 0 = never). */
-enum { HPFG_OPT_CONV_THIN = 0, HPFG_OPT_FIRST_MFMA = 1, HPFG_OPT_FIRST_WGRAD = 2, HPFG_OPT_NARROW_DEEP = 3, HPFG_OPT_COUNT = 4 };
+ *   (default 128: launches that would leave half of the CUs idle; 0 = never);
+ * HPFG_OPT_UPDATE_PACK: 0 = the optimizers never write weight fragments (hpfg_sgd_ema_pack_step is not used): every forward packs its own. */
+enum { HPFG_OPT_CONV_THIN = 0, HPFG_OPT_FIRST_MFMA = 1, HPFG_OPT_FIRST_WGRAD = 2, HPFG_OPT_NARROW_DEEP = 3, HPFG_OPT_UPDATE_PACK = 4, HPFG_OPT_COUNT = 5 };
+int hpfg_get_option(int which);
 int hpfg_set_option(int which, int value);
 
 /* ---- forward ------------------------------------------------------------------------------------------- */
@@ -237,6 +239,11 @@ int hpfg_reduce_partials(const float* partials, int nblk, int C, double* sums, v
 /* eval-mode BatchNorm (model.eval(), val.py:268-287): table rows from the running statistics */
 int hpfg_bn_eval_table(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
                        float* bn, int C, void* stream);
+/* hpfg_conv3x3_first_fwd[_acc] that also advances the two per-forward device counters of hpfg_pack_weights_bump (workgroup 0, before anything
+ * else): for a forward whose weight fragments are current, so that it starts without a pack launch.  stat_acc may be NULL (plain partial rows). */
+int hpfg_conv3x3_first_fwd_bump(const HpfgAct* x, const float* w_oihw, const float* bias, float* out, float* stat_partials, long long* stat_acc,
+                                int stat_shards, long long* counters, int n_counters, int32_t* seed_word, int seed_add, int N, int H, int W, int Cin,
+                                int Cout, void* stream);
 int hpfg_conv_kc(int H, int W, int taps);
 long hpfg_wpk16_elems(int Kchannels, int NchannelsPad, int taps, int kc);   /* bf16 elements of one wpk16 buffer */
 int hpfg_pack_weights(const HpfgPackDesc* table_dev, const HpfgPackDesc* table_host, int nlayers, void* stream);
@@ -540,6 +547,27 @@ int hpfg_ema_update(float* t, const float* s, long n, const float* alpha_dev, vo
  * (n_ema = n, or the leading backbone slice of main.py:68-76).  Bit-identical to hpfg_sgd_step followed by hpfg_ema_update. */
 int hpfg_sgd_ema_step(float* p, const float* g, float* mom, long n, const float* lr_dev, float momentum, float weight_decay, float grad_scale,
                       float* t, long n_ema, const float* alpha_dev, void* stream);
+
+/* hpfg_sgd_ema_step (t != NULL) or hpfg_sgd_step (t == NULL, n_ema 0, alpha_dev NULL) over [0, n) -- the same expressions, bit-identical
+ * results -- that also writes, from the NEW weights, what hpfg_pack_weights produces in bf16x3 mode for the listed conv layers: the student's
+ * fwd / dgrad fragments and padded bias rows and, from the new teacher weights, the teacher's fwd fragments and bias rows (bit-identical
+ * too).  Only positions that hold a weight are written: the padding of a fragment buffer must have been zeroed by one hpfg_pack_weights
+ * launch before.  Descriptors ascend in the flat buffer (weight, then bias of a layer); gaps = the ranges [lo, hi) between them, so that
+ * descriptors and gaps tile [0, n) exactly (checked: every element is updated once). */
+typedef struct HpfgUpdatePackDesc {
+  long w_off, b_off;    /* flat offsets of the layer's OIHW weight and of its bias */
+  void* wpk16_fwd;      /* student fragments as in HpfgPackDesc, or NULL */
+  void* wpk16_dgrad;    /* or NULL */
+  float* bias_pad;      /* [CoutPad] */
+  void* t_wpk16_fwd;    /* teacher fwd fragments (from the new teacher weights), or NULL */
+  float* t_bias_pad;    /* or NULL */
+  int32_t Cout, Cin, CoutPad, CinPad, taps;
+  int32_t kc, kc_t;     /* K packing of the student's / the teacher's buffers (hpfg_conv_kc) */
+  int32_t reserved;
+} HpfgUpdatePackDesc;
+int hpfg_sgd_ema_pack_step(float* p, const float* g, float* mom, long n, const float* lr_dev, float momentum, float weight_decay, float grad_scale,
+                           float* t, long n_ema, const float* alpha_dev, const HpfgUpdatePackDesc* table_dev, const HpfgUpdatePackDesc* table_host,
+                           int nlayers, const long* gaps_dev, const long* gaps_host, int ngaps, void* stream);
 
 /* ---- attention core on the matrix cores (SegFormer branch; reference model/segformer.py:92-128 after the q / kv projections) -------------- */
 /* out = softmax(scale * q k^T) v per (image, head): q [B,N,heads,32], kv [B,M,2,heads,32] (the kv Linear's output), M <= 64 keys, head dim 32;
