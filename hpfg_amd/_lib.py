@@ -19,7 +19,7 @@ OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP, OPT_UPDATE_PACK
 LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
 LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 140
+VERSION = 141
 RESIZE_TAPS = 36            # HPFG_RESIZE_TAPS: coefficients per output sample and axis of hpfg_resize_cubic's tap tables
 SURFACE_SEGS = 32           # HPFG_SURFACE_SEGS: surface-point segments of hpfg_surface_*, (class - 1) * 2 + side (0 = pred, 1 = gt)
 MATH_F32, MATH_BF16X3 = 0, 1
@@ -214,7 +214,7 @@ PROTOTYPES = {
     "hpfg_argmax_labels": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "hpfg_cutmix_blend": (_i, [_p, _p, _p, _p, _l, _p]),
     "hpfg_sgd_step": (_i, [_p, _p, _p, _l, _p, _f, _f, _f, _p]),
-    "hpfg_adamw_step": (_i, [_p, _p, _p, _p, _l, _p, _p, _f, _f, _f, _f, _f, _p]),
+    "hpfg_adamw_step": (_i, [_p, _p, _p, _p, _l, _p, _p, _d, _d, _f, _f, _f, _p]),
     "hpfg_ema_update": (_i, [_p, _p, _l, _p, _p]),
     "hpfg_sgd_ema_step": (_i, [_p, _p, _p, _l, _p, _f, _f, _f, _p, _l, _p, _p]),
     "hpfg_sgd_ema_pack_step": (_i, [_p, _p, _p, _l, _p, _f, _f, _f, _p, _l, _p, _p, C.POINTER(UpdatePackDesc), _i, _p, C.POINTER(C.c_long), _i, _p]),

@@ -463,18 +463,29 @@ __global__ __launch_bounds__(256) void sgd_ema_kernel(float* __restrict__ p, con
 }
 
 // torch.optim.AdamW (decoupled weight decay, bias-corrected moments) over flat buffers; *step_dev holds the number of steps already taken
-// (a one-thread kernel advances it afterwards, so a captured graph counts by itself)
+// (a one-thread kernel advances it afterwards, so a captured graph counts by itself).  The counter is a float32 word: it counts exactly up
+// to 2^24 = 16 777 216 steps (560 runs of the reference's 30 000 iterations); beyond that +1 no longer changes it.
+// The betas arrive as doubles and 1 - beta, 1 - beta^t are formed in double before they are rounded, as torch forms them on the host:
+// 1 - float(0.999) is 0.00099998713, 1.3e-5 off 0.001 -- every entry of v carried that factor (p did not: the float32 bias correction
+// carried it too).  One thread per workgroup computes the two corrections (two double pow) and hands them over through LDS.
 __global__ __launch_bounds__(256) HPFG_NO_PK_F32 void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                    long n, const float* __restrict__ lr_dev, const float* __restrict__ step_dev, float b1, float b2,
+                                                    long n, const float* __restrict__ lr_dev, const float* __restrict__ step_dev, double b1d, double b2d,
                                                     float eps, float wd, float gscale) {
-  const float lr = *lr_dev, t = *step_dev + 1.f;
-  const float bc1 = 1.f - powf(b1, t), bc2s = sqrtf(1.f - powf(b2, t));
+  __shared__ float bc[2];
+  if (threadIdx.x == 0) {
+    const double t = (double)*step_dev + 1.0;
+    bc[0] = (float)(1.0 - pow(b1d, t));
+    bc[1] = (float)sqrt(1.0 - pow(b2d, t));
+  }
+  __syncthreads();
+  const float lr = *lr_dev, bc1 = bc[0], bc2s = bc[1];
+  const float b1 = (float)b1d, b2 = (float)b2d, omb1 = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d);
   const float step_size = lr / bc1, decay = 1.f - lr * wd;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float gi = g[i] * gscale;
     const float w = p[i] * decay;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[i] + omb1 * gi;
+    const float vi = b2 * v[i] + omb2 * gi * gi;
     m[i] = mi;
     v[i] = vi;
     p[i] = w - step_size * mi / (sqrtf(vi) / bc2s + eps);
@@ -663,9 +674,10 @@ extern "C" int hpfg_sgd_ema_step(float* p, const float* g, float* mom, long n, c
   return hpfg_launch_status("sgd_ema_kernel");
 }
 
-extern "C" int hpfg_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* lr_dev, float* step_dev, float beta1, float beta2,
+extern "C" int hpfg_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* lr_dev, float* step_dev, double beta1, double beta2,
                                float eps, float weight_decay, float grad_scale, void* stream) {
   HPFG_ARG_CHECK(p && g && m && v && lr_dev && step_dev && n > 0, "adamw_step: bad args");
+  HPFG_ARG_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adamw_step: betas %g, %g outside [0, 1)", beta1, beta2);
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_dev, step_dev, beta1, beta2, eps,
                      weight_decay, grad_scale);
   hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_dev);

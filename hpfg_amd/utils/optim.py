@@ -173,9 +173,16 @@ def flatten_parameters(model):
 
 @torch.no_grad()
 def gather_flat_grads(model, active_numel=None):
-    """Pack the per-parameter gradients autograd left on a ``flatten_parameters`` module into ``model.flat_grads`` with ONE concat (a
-    parameter without a gradient contributes zeros).  active_numel: only the leading parameters that make up that many elements -- the
-    rest of the buffer is neither written here nor read by the optimizer kernels."""
+    """Pack the per-parameter gradients autograd left on a ``flatten_parameters`` module into ``model.flat_grads`` with ONE concat.
+    active_numel: only the leading parameters that make up that many elements -- the rest of the buffer is neither written here nor read
+    by the optimizer kernels.
+
+    Every parameter of the packed range must hold a gradient.  torch.optim.SGD / AdamW skip a parameter whose ``.grad`` is None (no weight
+    decay, no moment update); the flat kernels cannot skip a slice in the middle, and a gradient of zeros is NOT the same: the weight would
+    still decay and the moments shrink.  No module of this package has such a parameter: SegFormer, SegFormer_Plus and the Swin blocks
+    use every parameter they construct in every forward (``sr`` / ``norm`` of an Attention exist only where sr_ratio > 1, a
+    BasicBlock's ``downsample`` only where it is applied; a dropped path yields a zero gradient, not a missing one), and the one trailing
+    group a step leaves out -- the necks of HPFG's first student -- is cut off by active_numel.  Anything else is refused."""
     ps, k = [], 0
     for p in model.parameters():
         if active_numel is not None and k >= active_numel:
@@ -183,8 +190,14 @@ def gather_flat_grads(model, active_numel=None):
         ps.append(p)
         k += p.numel()
     assert active_numel is None or k == active_numel, "active_numel must end on a parameter boundary"
+    missing = [i for i, p in enumerate(ps) if p.grad is None]
+    if missing:
+        names = [n for i, (n, _) in enumerate(model.named_parameters()) if i in set(missing)]
+        raise RuntimeError(f"gather_flat_grads: {len(missing)} parameter(s) inside the updated range have no gradient ({', '.join(names[:4])}"
+                           f"{', ...' if len(names) > 4 else ''}): torch's optimizers would skip them, the flat kernels would decay them. "
+                           "Lay parameters that a step leaves out at the end of the module and set the optimizer's active_numel")
     out = model.flat_grads if active_numel is None else model.flat_grads[:k]
-    torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in ps], out=out)
+    torch.cat([p.grad.reshape(-1) for p in ps], out=out)
     return model.flat_grads
 
 

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 140
+#define HPFG_VERSION 141
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -536,8 +536,10 @@ int hpfg_bnrelu_bwd(const float* x, const float* dy, const float* mean, const fl
 int hpfg_sgd_step(float* p, const float* g, float* mom, long n, const float* lr_dev, float momentum, float weight_decay,
                   float grad_scale, void* stream);
 /* torch.optim.AdamW (utils/__init__.py:17-19: lr, weight_decay; betas (0.9, 0.999), eps 1e-8) over flat buffers; lr and the step count
- * (float, number of steps already taken; advanced by the call) are read from device memory, so the update replays inside a hipGraph */
-int hpfg_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* lr_dev, float* step_dev, float beta1, float beta2, float eps,
+ * (float, number of steps already taken, exact up to 2^24; advanced by the call) are read from device memory, so the update replays inside
+ * a hipGraph.  The betas are doubles: 1 - beta and the bias corrections 1 - beta^t are formed in double and then rounded, as torch forms
+ * them (1 - float(0.999) is 1.3e-5 off 0.001). */
+int hpfg_adamw_step(float* p, const float* g, float* m, float* v, long n, const float* lr_dev, float* step_dev, double beta1, double beta2, float eps,
                     float weight_decay, float grad_scale, void* stream);
 /* EMA teacher: t = alpha*t + (1-alpha)*s over flat buffers (utils/utils.py:82-86); alpha read from device */
 int hpfg_ema_update(float* t, const float* s, long n, const float* alpha_dev, void* stream);

@@ -169,3 +169,195 @@ def acc_from_rows(rows_f32, shards, device=None):
         acc[r % shards, ..., 1] += lo[r]
     t = torch.from_numpy(acc)
     return t if device is None else t.to(device)
+
+
+# ---- the optimizer kernels of csrc/misc.hip restated in numpy float32, and float64 references of the mixing kernels ---------------------
+import functools
+
+N_SMALL = 4099                      # odd, 17 workgroups
+N_BIG_OPTIM = 2048 * 256 + 257      # one element past a full pass of the optimizer launches (grid_for(n, 2048)): the grid-stride loop runs twice
+N_BIG_MIX = 4096 * 256 + 257        # the same for the launches capped at 4096 workgroups
+F32 = np.float32
+
+
+def f32_exact(x) -> float:
+    """The float32 a C `float` argument or a float32 device word holds for the Python float x, as a Python float: a float64 reference that
+    is handed these sees the same hyper-parameters as the kernel."""
+    return float(np.float32(x))
+
+
+def sgd_ema_f32(p, g_steps, mom, lrs, momentum, wd, gscale, t=None, n_ema=0, alphas=None):
+    """sgd_kernel / sgd_ema_kernel / ema_kernel (compiled with fp contract(off)) over len(lrs) steps, one float32 rounding per operation, in
+    torch.optim.SGD's order:  d = g*gscale + wd*w;  buf = momentum*buf + d;  w = w - lr*buf;  t[:n_ema] = t*a + w*(1 - a), 1 - a formed in
+    float32.  g_steps [steps][n].  -> (p, mom, t) float32 copies; the inputs are left alone."""
+    p, mom = np.array(p, dtype=F32), np.array(mom, dtype=F32)
+    t = None if t is None else np.array(t, dtype=F32)
+    mu, wd, gs = F32(momentum), F32(wd), F32(gscale)
+    for k, lr in enumerate(lrs):
+        g = np.asarray(g_steps[k], dtype=F32)
+        d = g * gs + wd * p
+        mom = mu * mom + d
+        p = p - F32(lr) * mom
+        if t is not None and n_ema > 0:
+            a = F32(alphas[k])
+            t[:n_ema] = t[:n_ema] * a + p[:n_ema] * (F32(1) - a)
+        assert p.dtype == F32 and mom.dtype == F32
+    return p, mom, t
+
+
+def sgd_ema_f64(p, g_steps, mom, lrs, momentum, wd, gscale, t, alphas):
+    """The same trajectory by torch.optim.SGD itself on float64 CPU tensors (gradient pre-multiplied by gscale) and a float64 EMA
+    t = t*a + w*(1 - a) over the whole buffer; hyper-parameters as the float32 words the kernel reads.  -> (p, mom, t) float64 numpy."""
+    w = torch.tensor(np.asarray(p), dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.SGD([w], lr=1.0, momentum=f32_exact(momentum), weight_decay=f32_exact(wd))
+    if momentum != 0:
+        opt.state[w]["momentum_buffer"] = torch.tensor(np.asarray(mom), dtype=torch.float64)      # (torch starts a missing buffer at d, not at 0*buf + d)
+    te = torch.tensor(np.asarray(t), dtype=torch.float64)
+    for k, lr in enumerate(lrs):
+        opt.param_groups[0]["lr"] = f32_exact(lr)
+        w.grad = torch.tensor(np.asarray(g_steps[k]), dtype=torch.float64) * f32_exact(gscale)
+        opt.step()
+        a = f32_exact(alphas[k])
+        te = te * a + w.detach() * (1.0 - a)
+    buf = opt.state[w]["momentum_buffer"].numpy() if momentum != 0 else None
+    return w.detach().numpy(), buf, te.numpy()
+
+
+SGD_LRS = (0.05, 0.031, 0.02, 0.011, 0.007)                     # another lr every step
+SGD_ALPHAS = tuple(min(1 - 1 / (k + 1), 0.99) for k in range(5))      # utils.ema_alpha(k, 0.99): 0 (the teacher becomes the student), 1/2, 2/3, ...
+SGD_HYPER = tuple((mu, wd, gs) for mu in (0.0, 0.9) for wd in (0.0, 5e-4) for gs in (1.0, 0.5, 1.0 / 3.0))
+
+
+@functools.lru_cache(maxsize=None)
+def sgd_case(n, seed=7):
+    """Weights, momentum buffer, teacher and five gradients of n elements for the SGD / EMA tests.  Computed once; read-only."""
+    r = np.random.RandomState(seed + n % 1000)
+    c = dict(p0=r.randn(n).astype(F32), mom0=(0.3 * r.randn(n)).astype(F32), t0=r.randn(n).astype(F32), g=r.randn(len(SGD_LRS), n).astype(F32))
+    for a in c.values():
+        a.setflags(write=False)
+    return c
+
+
+def sgd_f64_tolerances(p64, buf64, t64, g, wd, gscale, steps=len(SGD_LRS)):
+    """Bounds on |float32 restatement - float64 torch.optim.SGD| after `steps` steps, from the operation count (u = 2^-24, one rounding):
+    with B >= |g gscale| + wd |w| + |buf| and P >= |w|, M >= |t| + |w| over the trajectory (taken at its end with a factor 2 of slack),
+      buf: five roundings a step (g*gscale, wd*w, their sum, momentum*buf, the sum), each of a value <= B, and the inherited error
+           momentum * e_buf + wd * e_p <= e_buf + (negligible)                              -> e_buf <= steps * 6 u B
+      p:   lr*buf and the difference round once each (<= u lr B, u P), plus lr * e_buf       -> e_p  <= steps * (u P + lr (u B + e_buf))
+      t:   1 - a in float32 (error u, times |w|), two products and a sum (<= u M each), (1 - a) e_p  -> e_t <= steps * (4 u M + e_p)."""
+    u = 2.0 ** -24
+    B = 2.0 * float(np.abs(g).max() * abs(gscale) + wd * np.abs(p64).max() + (np.abs(buf64).max() if buf64 is not None else 0.0))
+    P, M = 2.0 * float(np.abs(p64).max()), 2.0 * float(np.abs(t64).max() + np.abs(p64).max())
+    e_buf = steps * 6 * u * B
+    e_p = steps * (u * P + max(SGD_LRS) * (u * B + e_buf))
+    return e_p, e_buf, steps * (4 * u * M + e_p)
+
+
+ADAMW_MUTATIONS = ("t_off_by_one", "no_sqrt_on_bc2", "eps_inside_root", "coupled_decay")
+ADAMW_CHECKED = (1, 2, 3, 10, 40)
+ADAMW_HP = dict(betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, grad_scale=0.5)
+
+
+def adamw_f32(p, g_steps, m, v, lrs, step0=0, betas=(0.9, 0.999), eps=1e-8, wd=0.05, gscale=0.5, mutation=None, checked=None):
+    """adamw_kernel in numpy float32 (the kernel's operation order; the kernel may contract a product into the following sum, this does
+    not).  mutation: one of ADAMW_MUTATIONS -- the mistakes the AdamW tolerance has to tell from rounding.  -> {step count: (p, m, v)} for
+    the counts in `checked` (default: the last one), counted from step0 + 1."""
+    assert mutation is None or mutation in ADAMW_MUTATIONS, mutation
+    p, m, v = (np.array(a, dtype=F32) for a in (p, m, v))
+    b1, b2, eps, wd, gs, one = F32(betas[0]), F32(betas[1]), F32(eps), F32(wd), F32(gscale), F32(1)
+    omb1, omb2 = F32(1.0 - betas[0]), F32(1.0 - betas[1])      # formed in double, then rounded (as the bias corrections below)
+    out = {}
+    for k, lr in enumerate(lrs):
+        lr = F32(lr)
+        t = step0 + k + 1
+        if mutation == "t_off_by_one":
+            t = t + 1
+        bc1 = F32(1.0 - float(betas[0]) ** t)
+        bc2 = 1.0 - float(betas[1]) ** t
+        bc2s = F32(bc2) if mutation == "no_sqrt_on_bc2" else F32(np.sqrt(bc2))
+        step_size, decay = lr / bc1, one - lr * wd
+        gi = np.asarray(g_steps[k], dtype=F32) * gs
+        w = p * decay
+        if mutation == "coupled_decay":
+            gi, w = gi + wd * p, p
+        m = b1 * m + omb1 * gi
+        v = b2 * v + omb2 * gi * gi
+        den = np.sqrt(v / (bc2s * bc2s) + eps) if mutation == "eps_inside_root" else np.sqrt(v) / bc2s + eps
+        p = w - step_size * m / den
+        assert p.dtype == F32 and m.dtype == F32 and v.dtype == F32 and np.asarray(bc1).dtype == F32
+        if checked is None or step0 + k + 1 in checked:
+            out[step0 + k + 1] = (p.copy(), m.copy(), v.copy())
+    if checked is None:
+        out = {step0 + len(lrs): out[step0 + len(lrs)]}
+    return out
+
+
+def adamw_torch(p, g_steps, lrs, dtype, betas=(0.9, 0.999), eps=1e-8, wd=0.05, gscale=0.5, checked=ADAMW_CHECKED):
+    """torch.optim.AdamW on CPU tensors of `dtype` from zero moments, gradient pre-multiplied by gscale.  -> {step count: (p, m, v)} numpy."""
+    w = torch.tensor(np.asarray(p), dtype=dtype, requires_grad=True)
+    opt = torch.optim.AdamW([w], lr=1.0, betas=betas, eps=eps, weight_decay=wd)
+    out = {}
+    for k, lr in enumerate(lrs):
+        opt.param_groups[0]["lr"] = float(lr)
+        w.grad = torch.tensor(np.asarray(g_steps[k]), dtype=dtype) * gscale
+        opt.step()
+        if k + 1 in checked:
+            s = opt.state[w]
+            out[k + 1] = (w.detach().numpy().copy(), s["exp_avg"].numpy().copy(), s["exp_avg_sq"].numpy().copy())
+    return out
+
+
+def cosine_warmup_lrs(steps, base_lr=1e-2):
+    """The learning rates the project's CosineWarmupLR_Scheduler hands an optimizer over `steps` iterations: a quarter of them warm-up (after the
+    reference's first-step quirk: the table's LAST entry), then the cosine; every step has another value."""
+    from hpfg_amd.utils import CosineWarmupLR_Scheduler
+    opt = torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=base_lr)
+    sched = CosineWarmupLR_Scheduler(opt, warmup_epochs=1, warmup_lr=1e-4, num_epochs=4, base_lr=base_lr, final_lr=1e-5, iter_per_epoch=steps // 4)
+    lrs = []
+    for _ in range(steps):
+        lrs.append(float(opt.param_groups[0]["lr"]))
+        opt.step()
+        sched.step()
+    return lrs
+
+
+@functools.lru_cache(maxsize=None)
+def adamw_case(n=N_SMALL, steps=40, seed=2024):
+    """The AdamW trajectory of the host and the GPU test: weights, per-step gradients whose per-element magnitudes are spread over
+    10^U(-8, 0) (elements near eps = 1e-8 pin where eps sits, large ones the bias corrections), the scheduler's learning rates, and for every
+    step in ADAMW_CHECKED torch.optim.AdamW in float64 (the reference), in float32, and the tolerance
+    tol[step][i] = 8 * max|float32 - float64| for i = p, m, v.  Computed once; treat as read-only."""
+    r = np.random.RandomState(seed)
+    p0 = r.randn(n).astype(F32)
+    mag = (10.0 ** r.uniform(-8.0, 0.0, n))
+    g = (mag[None, :] * r.randn(steps, n)).astype(F32)
+    lrs = cosine_warmup_lrs(steps)
+    ref64 = adamw_torch(p0, g, lrs, torch.float64)
+    ref32 = adamw_torch(p0, g, lrs, torch.float32)
+    ref_err = {s: tuple(float(np.abs(ref32[s][i].astype(np.float64) - ref64[s][i]).max()) for i in range(3)) for s in ref64}
+    tol = {s: tuple(8.0 * e for e in ref_err[s]) for s in ref_err}
+    for a in (p0, g):
+        a.setflags(write=False)
+    return dict(p0=p0, g=g, lrs=lrs, ref64=ref64, ref_err=ref_err, tol=tol)
+
+
+def adamw_errors(got, ref64):
+    """{step: (max|dp|, max|dm|, max|dv|)} of {step: (p, m, v)} against the float64 run."""
+    return {s: tuple(float(np.abs(np.asarray(got[s][i], dtype=np.float64) - ref64[s][i]).max()) for i in range(3)) for s in got}
+
+
+def adamw_within(err, tol):
+    return all(err[s][i] <= tol[s][i] for s in err for i in range(3))
+
+
+def blend_f64(a, b, m):
+    """a(1 - m) + b m in float64 (cutmix_kernel, mix_samples_kernel) and the issue's elementwise bound 3 * 2^-24 * (|a| + |b|): 1 - m, two
+    products and a sum, each rounded once (or a product fused into the sum), every intermediate at most |a| + |b|."""
+    a, b, m = (np.asarray(x, dtype=np.float64) for x in (a, b, m))
+    return a * (1.0 - m) + b * m, 3.0 * 2.0 ** -24 * (np.abs(a) + np.abs(b))
+
+
+def softmax_mix_f64(t0, t1, f):
+    """softmax(t0, dim 1)(1 - f[s]) + softmax(t1, dim 1) f[s] of [n,C,H,W] logits in float64 (torch, CPU)."""
+    w = torch.as_tensor(f, dtype=torch.float64).reshape(-1, 1, 1, 1)
+    return torch.softmax(t0.double(), 1) * (1.0 - w) + torch.softmax(t1.double(), 1) * w

@@ -308,3 +308,108 @@ def test_acc_encode_reproduces_the_exact_limb_split_of_hpfg_acc_add():
     # 2048 adds of the largest low limb stay inside an int64 word; the Python-integer totals do not wrap beyond it either
     worst = torch.full((8, 2, 1, 2), 2048 * 2 ** 51, dtype=torch.int64)
     assert int(acc_totals(worst, 1, 8)[0, 0, 1]) == 2 ** 65
+
+
+def test_sgd_ema_restatement_follows_torch_sgd_in_float64():
+    """tests/helpers.py::sgd_ema_f32 -- the float32 restatement the GPU test requires hpfg_sgd_step / hpfg_sgd_ema_step / hpfg_ema_update to
+    equal bit for bit -- against torch.optim.SGD itself on float64 tensors and a float64 EMA, over five steps with another lr (and EMA
+    alpha) each, for every momentum / weight-decay / grad_scale combination of the GPU test: the bit-equality is then a statement about the
+    real optimizer, not about the kernel's own expressions.  The bound is derived in helpers.sgd_f64_tolerances (at most 1.3e-5 for the weights
+    here: a few ulp of max|w| per step); a flipped weight-decay sign moves a weight by 2 lr wd |w| ~ 2.5e-5 |w| a step, momentum and
+    grad_scale swapped by far more."""
+    from tests.helpers import N_SMALL, SGD_ALPHAS, SGD_HYPER, SGD_LRS, sgd_case, sgd_ema_f32, sgd_ema_f64, sgd_f64_tolerances
+    c = sgd_case(N_SMALL)
+    n = N_SMALL
+    for mu, wd, gs in SGD_HYPER:
+        p32, b32, t32 = sgd_ema_f32(c["p0"], c["g"], c["mom0"], SGD_LRS, mu, wd, gs, t=c["t0"], n_ema=n, alphas=SGD_ALPHAS)
+        p64, b64, t64 = sgd_ema_f64(c["p0"], c["g"], c["mom0"], SGD_LRS, mu, wd, gs, c["t0"], SGD_ALPHAS)
+        tol_p, tol_b, tol_t = sgd_f64_tolerances(p64, b64, t64, c["g"], wd, gs)
+        assert tol_p < 2e-5 and tol_t < 2e-4, (tol_p, tol_t)          # (the bound itself stays at the rounding level: |w| reaches 4, five steps)
+        e_p, e_t = np.abs(p32 - p64).max(), np.abs(t32 - t64).max()
+        assert e_p <= tol_p and e_t <= tol_t, (mu, wd, gs, e_p, tol_p, e_t, tol_t)
+        if mu != 0:
+            assert np.abs(b32 - b64).max() <= tol_b, (mu, wd, gs)
+        # the mistakes the issue names are far outside: weight-decay sign (where there is decay), momentum and grad_scale swapped
+        if wd != 0:
+            bad = sgd_ema_f32(c["p0"], c["g"], c["mom0"], SGD_LRS, mu, -wd, gs)[0]
+            assert np.abs(bad - p64).max() > 10 * tol_p
+        if mu != gs:
+            bad = sgd_ema_f32(c["p0"], c["g"], c["mom0"], SGD_LRS, gs, wd, mu)[0]
+            assert np.abs(bad - p64).max() > 10 * tol_p
+    # a partial teacher slice leaves the rest of the teacher alone; alpha = 0 at the first step makes the slice the fresh student
+    p1, _, t1 = sgd_ema_f32(c["p0"], c["g"][:1], c["mom0"], SGD_LRS[:1], 0.9, 5e-4, 0.5, t=c["t0"], n_ema=1001, alphas=(0.0,))
+    assert np.array_equal(t1[:1001], p1[:1001]) and np.array_equal(t1[1001:], c["t0"][1001:])
+
+
+def test_adamw_restatement_passes_the_reference_bound_and_every_mutation_fails_it():
+    """The tolerance of tests/test_gpu_optim.py::test_adamw_kernel_trajectory is 8 x the error torch.optim.AdamW in float32 makes against
+    torch.optim.AdamW in float64 on the same 40-step trajectory (helpers.adamw_case), per checked step and per buffer.  That bound must
+    tell a correct kernel from a subtly wrong one: the numpy float32 restatement of the kernel passes it, and each of the four mistakes
+    (t off by one, no sqrt on the second bias correction, eps inside the root, weight decay coupled into the gradient) fails it.
+    Measured on the committed trajectory, max|dp| at step 40: reference float32 1.6e-6, restatement 1.6e-6, t+1 1.2e-3, no sqrt 1.2e-1,
+    eps inside the root 1.2e-1, coupled decay 3.2e-1."""
+    from tests.helpers import ADAMW_CHECKED, ADAMW_MUTATIONS, N_SMALL, adamw_case, adamw_errors, adamw_f32, adamw_within
+    c = adamw_case()
+    lrs = c["lrs"]
+    assert len(set(lrs)) >= len(lrs) - 1 and np.argmax(lrs) in range(5, 20)          # warm-up inside the 40 steps; lr moves at every step
+    assert set(c["ref64"]) == set(ADAMW_CHECKED) and all(e > 0 for s in c["ref_err"] for e in c["ref_err"][s])
+    mags = np.abs(c["g"]).max(0)
+    assert (mags < 1e-7).mean() > 0.05 and (mags > 1e-1).mean() > 0.05               # gradients around eps and around 1
+    z = np.zeros(N_SMALL, np.float32)
+    ok = adamw_errors(adamw_f32(c["p0"], c["g"], z, z, lrs, checked=ADAMW_CHECKED), c["ref64"])
+    assert adamw_within(ok, c["tol"]), (ok, c["tol"])
+    for mut in ADAMW_MUTATIONS:
+        bad = adamw_errors(adamw_f32(c["p0"], c["g"], z, z, lrs, mutation=mut, checked=ADAMW_CHECKED), c["ref64"])
+        assert not adamw_within(bad, c["tol"]), mut
+        assert bad[40][0] > 10 * c["tol"][40][0], (mut, bad[40][0], c["tol"][40][0])      # ... by a wide margin in the weights
+    # a restart from saved moments continues the same trajectory (what FusedAdamW.load_state_dict relies on)
+    a = adamw_f32(c["p0"], c["g"][:6], z, z, lrs[:6])[6]
+    b = adamw_f32(a[0], c["g"][6:12], a[1], a[2], lrs[6:12], step0=6)[12]
+    whole = adamw_f32(c["p0"], c["g"][:12], z, z, lrs[:12])[12]
+    assert all(np.array_equal(x, y) for x, y in zip(b, whole))
+
+
+def test_mixing_references_and_bounds():
+    """helpers.blend_f64 / softmax_mix_f64, the float64 references of the blend and ICT kernels: 0/1 weights select exactly, the bound
+    3 * 2^-24 (|a| + |b|) holds for the blend evaluated in float32 on the host, rows of the mixed softmax sum to 1."""
+    from tests.helpers import blend_f64, softmax_mix_f64
+    r = np.random.RandomState(3)
+    a, b = r.randn(4099).astype(np.float32), (r.randn(4099) * 50).astype(np.float32)
+    m = r.choice([0.0, 1.0], 4099).astype(np.float32)
+    ref, bound = blend_f64(a, b, m)
+    assert np.array_equal(ref, np.where(m == 1, b, a).astype(np.float64)) and (bound > 0).all()
+    m = r.uniform(0, 1, 4099).astype(np.float32)
+    ref, bound = blend_f64(a, b, m)
+    got = a * (np.float32(1) - m) + b * m
+    assert got.dtype == np.float32 and (np.abs(got - ref) <= bound).all()
+    t0, t1 = torch.randn(3, 9, 4, 5) * 8, torch.randn(3, 9, 4, 5) * 8
+    out = softmax_mix_f64(t0, t1, [0.0, 1.0, 0.25])
+    assert torch.equal(out[0], torch.softmax(t0.double(), 1)[0]) and torch.equal(out[1], torch.softmax(t1.double(), 1)[1])
+    assert float((out.sum(1) - 1).abs().max()) < 1e-14
+
+
+def test_gather_flat_grads_refuses_a_parameter_without_gradient_inside_the_range():
+    """torch.optim.AdamW skips a parameter whose .grad is None; the flat AdamW / SGD kernels cannot, and zeros in its place would still decay
+    the weight.  No module of the package leaves a parameter of the updated range without a gradient, so gather_flat_grads raises where
+    one is met (naming it) instead of packing zeros; past active_numel nothing is looked at or written."""
+    from hpfg_amd.utils.optim import flatten_parameters, gather_flat_grads
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3))
+    flatten_parameters(net)
+    n0 = 7 * 5 + 5
+    assert net.flat_params.numel() == n0 + 5 * 3 + 3 and all(p.data_ptr() >= net.flat_params.data_ptr() for p in net.parameters())
+    for p in net[0].parameters():
+        p.grad = torch.randn_like(p)
+    net.flat_grads.fill_(7.0)
+    out = gather_flat_grads(net, n0)                       # the second layer has no gradients: outside the range, fine
+    assert torch.equal(out[:n0], torch.cat([p.grad.reshape(-1) for p in net[0].parameters()])) and bool((out[n0:] == 7.0).all())
+    with pytest.raises(RuntimeError, match=r"1\.weight"):
+        gather_flat_grads(net)                             # ... inside it: refused
+    net[0].bias.grad = None
+    with pytest.raises(RuntimeError, match=r"0\.bias"):
+        gather_flat_grads(net, n0)
+    with pytest.raises(AssertionError):
+        gather_flat_grads(net, n0 - 1)                     # not a parameter boundary
+    for p in net.parameters():
+        p.grad = torch.ones_like(p)
+    assert bool((gather_flat_grads(net) == 1.0).all())
