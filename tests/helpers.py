@@ -41,11 +41,10 @@ def pad16(c):
 
 class AdHocConv:
     def __init__(self, cin, cout, taps, device, seed=0, hw=(16, 16)):
-        g = torch.Generator().manual_seed(seed)
         k = 3 if taps == 9 else 1
         self.cin, self.cout, self.taps, self.k, self.dev = cin, cout, taps, k, device
-        self.w = (torch.randn(cout, cin, k, k, generator=g) * 0.2).to(device)
-        self.b = torch.randn(cout, generator=g).to(device)
+        w, b = adhoc_weights(cin, cout, taps, seed)
+        self.w, self.b = w.to(device), b.to(device)
         self.cin_pad, self.cout_pad = pad16(cin), pad16(cout)
         n = taps * self.cin_pad * self.cout_pad
         self.wpk_f = torch.empty(n, device=device)
@@ -64,13 +63,17 @@ class AdHocConv:
         self._keep = (d, dev_tab)
         L.check(L.load().hpfg_pack_weights(dev_tab.data_ptr(), d, 1, stream(device)), "pack")
 
-    def conv(self, a0, a1, N, H, W, stats=False, dgrad=False, math=0, stat_acc=None, shards=1, bwd_stats=0, bwd_of=None):
+    def conv(self, a0, a1, N, H, W, stats=False, dgrad=False, math=0, stat_acc=None, shards=1, bwd_stats=0, bwd_of=None,
+             out_pstride=None, out_coff=0, out_split=0, out2_pstride=None, out2_coff=0, stage_out=None, side_sums=None):
         """stat_acc / shards: with stats=True the BatchNorm sums ALSO go into this zeroed accumulator (HpfgConvArgs.stat_acc), next to the rows
-        of partial sums.  bwd_stats / bwd_of: the dgrad epilogue's backward sums (HpfgConvArgs.bwd_stats).  self.rows = rows the launch wrote."""
+        of partial sums.  bwd_stats / bwd_of: the dgrad epilogue's backward sums (HpfgConvArgs.bwd_stats).  self.rows = rows the launch wrote.
+        out_pstride / out_coff: the output lives at channel offset out_coff of a NaN-prefilled buffer of out_pstride floats per pixel, which is
+        what is returned.  out_split / out2_pstride / out2_coff: output channels >= out_split go to a second such buffer, self.out2.
+        stage_out / side_sums: tensors the launch fills (HpfgConvArgs.stage_out, .side_sums)."""
         lib = L.load()
         cout = self.cin if dgrad else self.cout
         cpad = self.cin_pad if dgrad else self.cout_pad
-        out = torch.full((N, H, W, cout), float("nan"), device=self.dev)
+        out = torch.full((N, H, W, out_pstride or cout), float("nan"), device=self.dev)
         ca = L.ConvArgs()
         ca.a0, ca.a1 = a0, (a1 if a1 is not None else L.Act())
         ca.math = math
@@ -80,7 +83,6 @@ class AdHocConv:
         else:
             ca.wpk = L.ptr(self.wpk_d if dgrad else self.wpk_f)
         ca.bias = None if dgrad else L.ptr(self.bias_pad)
-        ca.out = L.ptr(out)
         part = None
         if stats:
             part = torch.zeros(lib.hpfg_conv_stat_blocks(N, H, W) * 2 * cpad, device=self.dev)   # unused rows stay 0
@@ -90,17 +92,26 @@ class AdHocConv:
                 ca.stat_acc, ca.stat_shards = L.ptr(stat_acc), shards
         if bwd_stats:
             ca.bwd_stats, ca.bwd_of = bwd_stats, bwd_of
-        ca.out_pstride, ca.Cout, ca.CoutPad, ca.N, ca.H, ca.W, ca.taps = cout, cout, cpad, N, H, W, self.taps
-        self.rows = lib.hpfg_conv_stat_rows(C.byref(ca)) if stats else 0
+        ca.out_pstride, ca.Cout, ca.CoutPad, ca.N, ca.H, ca.W, ca.taps = out_pstride or cout, cout, cpad, N, H, W, self.taps
+        ca.out = out.data_ptr() + 4 * out_coff
+        self.out2 = None
+        if out_split:
+            self.out2 = torch.full((N, H, W, out2_pstride or cout - out_split), float("nan"), device=self.dev)
+            ca.out2, ca.out_split, ca.out2_pstride = self.out2.data_ptr() + 4 * out2_coff, out_split, self.out2.shape[-1]
+        ca.stage_out, ca.side_sums = L.ptr(stage_out), L.ptr(side_sums)
+        self.rows = lib.hpfg_conv_stat_rows(C.byref(ca)) if (stats or side_sums is not None) else 0
         L.check(lib.hpfg_conv_fwd(C.byref(ca), stream(self.dev)), "conv_fwd")
         return out, part
 
-    def wgrad(self, a0, a1, g, N, H, W, math=0):
+    def wgrad(self, a0, a1, g, N, H, W, math=0, slab_nan=False):
+        """slab_nan: the slab workspace starts as NaN, so that a slab the launch leaves unwritten shows in the reduced gradient."""
         lib = L.load()
         wa = L.WgradArgs()
         wa.a0, wa.a1, wa.g = a0, (a1 if a1 is not None else L.Act()), g
         S = lib.hpfg_wgrad_splits(N, H, W, self.cin_pad, self.cout_pad, self.taps)
         slab = torch.empty(lib.hpfg_wgrad_slab_floats(N, H, W, self.cin_pad, self.cout_pad, self.taps), device=self.dev)
+        if slab_nan:
+            slab.fill_(float("nan"))
         dw = torch.full_like(self.w, float("nan"))
         wa.slab, wa.dw_oihw, wa.math = L.ptr(slab), L.ptr(dw), math
         wa.Cin, wa.CinPad, wa.Cout, wa.CoutPad, wa.N, wa.H, wa.W, wa.taps, wa.S = self.cin, self.cin_pad, self.cout, self.cout_pad, N, H, W, self.taps, S
@@ -361,3 +372,334 @@ def softmax_mix_f64(t0, t1, f):
     """softmax(t0, dim 1)(1 - f[s]) + softmax(t1, dim 1) f[s] of [n,C,H,W] logits in float64 (torch, CPU)."""
     w = torch.as_tensor(f, dtype=torch.float64).reshape(-1, 1, 1, 1)
     return torch.softmax(t0.double(), 1) * (1.0 - w) + torch.softmax(t1.double(), 1) * w
+
+
+# ---- float64 restatements of the virtual sources (csrc/stage.h, csrc/common.h act_load4) and the error bound of the split-bf16 kernels ----
+# Plain torch / numpy float64 functions of the raw tensors (NHWC) and the table rows; they call no project kernel.  Each returns the value
+# and `delta`, the bound on what the fp32 evaluation of the chain may differ from it (u = 2^-24, one rounding per operation, an FMA or a
+# separate multiply and add alike), stated once per kind beside the code.
+import torch.nn.functional as F
+
+U24 = 2.0 ** -24
+LEAKY32 = f32_exact(0.01)          # HPFG_LEAKY as the float the kernels multiply by
+
+
+def bn_table(C_, seed):
+    """A hand-made BatchNorm table [BN_ROWS][C] (float32): mean, rstd, scale = gamma * rstd, shift = beta - mean * scale, k1 .. k3 random."""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.zeros(L.BN_ROWS, C_)
+    t[L.BN_MEAN] = torch.randn(C_, generator=g) * 0.3
+    t[L.BN_RSTD] = torch.rand(C_, generator=g) + 0.5
+    gamma = torch.randn(C_, generator=g)
+    beta = torch.randn(C_, generator=g) * 0.2
+    t[L.BN_SCALE] = gamma * t[L.BN_RSTD]
+    t[L.BN_SHIFT] = beta - t[L.BN_MEAN] * t[L.BN_SCALE]
+    t[L.BN_K1], t[L.BN_K2], t[L.BN_K3] = torch.randn(3, C_, generator=g) * 0.5
+    return t
+
+
+def lrelu_slope(z64, sc, sh):
+    """LeakyReLU'(z * scale + shift) as the kernels decide it in fp32; the inputs must keep every decision clear of the rounding of y."""
+    y = z64 * sc + sh
+    assert not bool((y.abs() <= 2.0 ** -22 * torch.maximum((z64 * sc).abs(), sh.abs().expand_as(y))).any()), "test input sits on a LeakyReLU tie"
+    return torch.where(y > 0, torch.ones_like(y), torch.full_like(y, 0.01))
+
+
+def keep_f64(shape, p, seed):
+    """keep / (1 - p) of an NHWC tensor of `shape`: oracle.rng_ref.keep_mask_nhwc over element index pix * C + c; p as the float the kernel holds."""
+    if p <= 0:
+        return torch.ones(shape, dtype=torch.float64)
+    n = int(np.prod(shape))
+    keep = torch.from_numpy(rng_ref.keep_mask_nhwc(n, p, seed).astype(np.float64)).reshape(shape)
+    return keep / (1.0 - f32_exact(p))
+
+
+def _act64(z, sc, sh):
+    """lrelu(z * scale + shift) and the magnitude |z scale| + |shift| its roundings are relative to"""
+    z, sc, sh = z.double(), sc.double(), sh.double()
+    y = z * sc + sh
+    return torch.where(y > 0, y, LEAKY32 * y), (z * sc).abs() + sh.abs()
+
+
+def bnact_f64(z, sc, sh, p=0.0, seed=0):
+    """lrelu(z * scale + shift) * keep / (1 - p).
+    delta = 6 u (|z scale| + |shift|) / (1 - p): the product and the sum of y (2), the LeakyReLU product (1), 1 - p, its reciprocal and the
+    dropout product (3), each relative to a value of at most that magnitude."""
+    a, mag = _act64(z, sc, sh)
+    k = keep_f64(a.shape, p, seed)
+    return a * k, 6.0 * U24 * mag / (1.0 - f32_exact(p))
+
+
+def pool_windows(a):
+    """[N, 2H, 2W, C] -> [4][N, H, W, C]: the window elements in row-major order (0,0), (0,1), (1,0), (1,1)"""
+    return torch.stack([a[:, 0::2, 0::2], a[:, 0::2, 1::2], a[:, 1::2, 0::2], a[:, 1::2, 1::2]])
+
+
+def pool_f64(z2, sc, sh):
+    """max of the four activated values of a 2 x 2 window (no dropout in front of a pool).
+    delta = 3 u max over the window of (|z scale| + |shift|): y (2) and the LeakyReLU product (1); a maximum moves by at most what its
+    arguments move."""
+    a, mag = _act64(z2, sc, sh)
+    return pool_windows(a).max(0).values, 3.0 * U24 * pool_windows(mag).max(0).values
+
+
+def pool_argmax(a, delta=None):
+    """index 0 .. 3 of the first maximum of every window of a [N, 2H, 2W, C] in row-major order.  With `delta` (bound on the fp32 rounding of
+    a): the top two values of every window must be further apart than both may move -- the arg-max guard of the test inputs."""
+    w = pool_windows(a)
+    first = torch.full(w.shape[1:], 3, dtype=torch.int64)
+    for k in (2, 1, 0):                                  # the lowest index among equal maxima, stated rather than left to argmax
+        first = torch.where(w[k] == w.max(0).values, torch.full_like(first, k), first)
+    if delta is not None:
+        top2 = w.topk(2, dim=0).values
+        assert bool(((top2[0] - top2[1]) > 2.0 * pool_windows(delta).max(0).values).all()), "test input sits on a max-pool tie"
+    return first
+
+
+def pool_scatter_f64(dP, first):
+    """MaxPool2d(2) backward: dP [N, H, W, C] placed at the arg-max `first` (pool_argmax) of every window -> [N, 2H, 2W, C], zero elsewhere."""
+    n, h, w, c = dP.shape
+    out = torch.zeros(n, 2 * h, 2 * w, c, dtype=torch.float64)
+    for k in range(4):
+        out[:, (k >> 1)::2, (k & 1)::2] = torch.where(first == k, dP.double(), torch.zeros((), dtype=torch.float64))
+    return out
+
+
+def up2x_matrix(Lo):
+    """(M, E): M = the [2 Lo][Lo] float64 matrix of the align_corners=True bilinear x2 along one axis, its weights formed in float32 by the
+    kernels' law: ratio (in - 1) / (out - 1) as a float, times the output index, truncated; w1 = f - i0, w0 = 1 - w1.  E = what the fp32
+    rounding of f = ratio * index may do to a row of M: the product rounds once (u f), or not at all where the compiler contracts it into
+    f - i0, so a kernel's w1 lies within u f of the law's -- E[o] = u f (e_i1 - e_i0)."""
+    m, e = np.zeros((2 * Lo, Lo), dtype=np.float64), np.zeros((2 * Lo, Lo), dtype=np.float64)
+    r = F32(Lo - 1) / F32(2 * Lo - 1) if Lo > 1 else F32(0)
+    for o in range(2 * Lo):
+        f = F32(r * F32(o))
+        i0 = int(f)
+        i1 = i0 + (1 if i0 < Lo - 1 else 0)
+        w1 = F32(f - F32(i0))
+        w0 = F32(F32(1) - w1)
+        m[o, i0] += float(w0)
+        m[o, i1] += float(w1)
+        e[o, i0] -= U24 * float(f)
+        e[o, i1] += U24 * float(f)
+    return torch.from_numpy(m), torch.from_numpy(e)
+
+
+def up2x_f64(u):
+    """bilinear x2 (align_corners=True) of u [N, h, w, C] -> [N, 2h, 2w, C], blended in float64.
+    delta = 6 u * (the same blend of |u|) + |E_y u M_x| + |M_y u E_x|: four products, three sums, 1 - w twice share out to under six roundings
+    of partial results that the blend of magnitudes bounds; a weight within u f of the law's (up2x_matrix) moves the value by that times the
+    difference of the two rows (columns) it blends."""
+    (my, ey), (mx, ex) = up2x_matrix(u.shape[1]), up2x_matrix(u.shape[2])
+    u = u.double()
+    blend = lambda a, t, b: torch.einsum("yi,nijc,xj->nyxc", a, t, b)
+    return blend(my, u, mx), 6.0 * U24 * blend(my, u.abs(), mx) + blend(ey, u, mx).abs() + blend(my, u, ex).abs()
+
+
+def upbwd_f64(g):
+    """the transpose of that interpolation applied to a gradient g [N, 2h, 2w, C] -> [N, h, w, C].
+    delta = 12 u * (the transpose applied to |g|) + |E_y|^T |g M_x| + |M_y^T g| |E_x|: up to 5 x 5 taps gathered as five horizontal FMAs and one
+    vertical FMA per row (the weight of a doubled tap is one more sum); the weights within u f of the law's, each output row (column) on its
+    own."""
+    (my, ey), (mx, ex) = up2x_matrix(g.shape[1] // 2), up2x_matrix(g.shape[2] // 2)
+    g = g.double()
+    d = torch.einsum("yi,nyxc,xj->nijc", my, g, mx)
+    dw = torch.einsum("yi,nyjc->nijc", ey.abs(), torch.einsum("nyxc,xj->nyjc", g, mx).abs()) + \
+        torch.einsum("nixc,xj->nijc", torch.einsum("yi,nyxc->nixc", my, g).abs(), ex.abs())
+    return d, 12.0 * U24 * torch.einsum("yi,nyxc,xj->nijc", my, g.abs(), mx) + dw
+
+
+def cat_f64(z, sc, sh, u):
+    """[bnact (no dropout) | up2x] along the channels; delta of each half by its own law."""
+    a, da = bnact_f64(z, sc, sh)
+    b, db = up2x_f64(u)
+    return torch.cat([a, b], -1), torch.cat([da, db], -1)
+
+
+def dz_f64(z, dA, tab, p=0.0, seed=0):
+    """k1 * g + (k2 * z + k3) with g = dA * keep / (1 - p) * slope(z * scale + shift); tab = the table rows [BN_ROWS][C].
+    delta = 6 u (|k1 g| + |k2 z| + |k3|): 1 - p, its reciprocal, the dropout and the slope products (4) and k1 * g and the final sum (2) on the
+    first term; k2 * z, + k3 and the final sum (3) on the rest."""
+    t = tab.double()
+    z = z.double()
+    slope = torch.where(lrelu_slope(z, t[L.BN_SCALE], t[L.BN_SHIFT]) == 1.0, 1.0, LEAKY32)      # (the float the kernels multiply by)
+    g = dA.double() * keep_f64(z.shape, p, seed) * slope
+    v = t[L.BN_K1] * g + (t[L.BN_K2] * z + t[L.BN_K3])
+    return v, 6.0 * U24 * ((t[L.BN_K1] * g).abs() + (t[L.BN_K2] * z).abs() + t[L.BN_K3].abs())
+
+
+def materialized_within_delta(got, kind, z, tab, u=None, dA=None, p=0.0, seed=0):
+    """hpfg_act_materialize's result `got` (the act_load4 copy of the producer chain, csrc/common.h) against the float64 restatement of that
+    kind from the raw CPU tensors, within the kind's delta.  -> largest error / delta; asserts it is at most 1."""
+    sc, sh = tab[L.BN_SCALE], tab[L.BN_SHIFT]
+    if kind == "plain":
+        v, d = z.double(), None
+    elif kind == "bnact":
+        v, d = bnact_f64(z, sc, sh, p, seed)
+    elif kind == "pool":
+        v, d = pool_f64(z, sc, sh)
+    elif kind == "cat":
+        v, d = cat_f64(z, sc, sh, u)
+    else:
+        v, d = dz_f64(z, dA, tab, p, seed)
+    err = (got.detach().cpu().double() - v).abs()
+    if d is None:
+        assert float(err.max()) == 0.0
+        return 0.0
+    ratio = float((err / d).max())
+    assert ratio <= 1.0, f"hpfg_act_materialize ({kind}) is {ratio:.3g} x delta off the float64 restatement"
+    return ratio
+
+
+# The kernels form hi*hi + hi*lo + lo*hi with hi = bf16(x), lo = bf16(x - hi) and accumulate in fp32.  Per output element, with
+# S = sum |a||w| (+ |bias|) over its T terms:
+#   3 * 2^-16 * S        each operand is represented to 2^-16 relative (2), the dropped lo*lo term is at most 2^-16 (1)
+#   (T + 2) * 2^-24 * S  the fp32 sum
+#   sum |w| * delta_a    the fp32 rounding of the source chain, per kind as stated above
+def _split_bound(S, T, chain):
+    return 3.0 * 2.0 ** -16 * S + (T + 2) * U24 * S + chain
+
+
+def conv_ref_bound(a, da, w, b):
+    """a, da [N,H,W,Cin] float64 (value, delta), w [Cout,Cin,k,k], b [Cout] or None -> (F.conv2d in float64, bound), both [N,H,W,Cout]"""
+    pad = w.shape[-1] // 2
+    w64, x = w.double(), nchw(a)
+    ref = F.conv2d(x, w64, None if b is None else b.double(), padding=pad)
+    S = F.conv2d(x.abs(), w64.abs(), None if b is None else b.double().abs(), padding=pad)
+    chain = F.conv2d(nchw(da), w64.abs(), None, padding=pad)
+    T = w[0].numel() + (0 if b is None else 1)
+    return ref.permute(0, 2, 3, 1).contiguous(), _split_bound(S, T, chain).permute(0, 2, 3, 1).contiguous()
+
+
+def dgrad_ref_bound(g, dg, w):
+    """g, dg [N,H,W,Cout] float64 -> (float64 autograd of F.conv2d w.r.t. its input, bound), both [N,H,W,Cin]"""
+    pad = w.shape[-1] // 2
+    w64 = w.double()
+    n, h, wd, _ = g.shape
+    x = torch.zeros(n, w.shape[1], h, wd, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, w64, None, padding=pad).backward(nchw(g))
+    S = F.conv_transpose2d(nchw(g).abs(), w64.abs(), padding=pad)
+    chain = F.conv_transpose2d(nchw(dg), w64.abs(), padding=pad)
+    T = w.shape[0] * w.shape[2] * w.shape[3]
+    return x.grad.permute(0, 2, 3, 1).contiguous(), _split_bound(S, T, chain).permute(0, 2, 3, 1).contiguous()
+
+
+def wgrad_ref_bound(a, da, g, dg, wshape):
+    """a, da [N,H,W,Cin], g, dg [N,H,W,Cout] float64 -> (float64 autograd of F.conv2d w.r.t. its weight, bound), both [Cout,Cin,k,k]; the sum
+    runs over the pixels: T = N * H * W, the chain term |a| dg + da |g| + da dg"""
+    from torch.nn import grad as G
+    pad = wshape[-1] // 2
+    x = nchw(a)
+    wr = torch.zeros(wshape, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, wr, None, padding=pad).backward(nchw(g))
+    cw = lambda p_, q_: G.conv2d_weight(nchw(p_), wshape, nchw(q_), padding=pad)
+    S = cw(a.abs(), g.abs())
+    chain = cw(a.abs(), dg) + cw(da, g.abs()) + cw(da, dg)
+    return wr.grad, _split_bound(S, a.shape[0] * a.shape[1] * a.shape[2], chain)
+
+
+def f32_conv_ratio(kind, ref, bound, *args):
+    """largest error / bound that torch float32 on the CPU reaches on the same (float64-derived) operands: kind = "conv" (a, w, b),
+    "dgrad" (g, w) or "wgrad" (a, g, wshape)"""
+    if kind == "conv":
+        a, w, b = args
+        got = F.conv2d(nchw(a).float(), w.float(), None if b is None else b.float(), padding=w.shape[-1] // 2).permute(0, 2, 3, 1)
+    elif kind == "dgrad":
+        g, w = args
+        x = torch.zeros(g.shape[0], w.shape[1], g.shape[1], g.shape[2], requires_grad=True)
+        F.conv2d(x, w.float(), None, padding=w.shape[-1] // 2).backward(nchw(g).float())
+        got = x.grad.permute(0, 2, 3, 1)
+    else:
+        a, g, wshape = args
+        wr = torch.zeros(wshape, requires_grad=True)
+        F.conv2d(nchw(a).float(), wr, None, padding=wshape[-1] // 2).backward(nchw(g).float())
+        got = wr.grad
+    return float(((got.double() - ref).abs() / bound).max())
+
+
+def adhoc_weights(cin, cout, taps, seed):
+    """weight [cout, cin, k, k] and bias [cout] (float32, CPU) of AdHocConv(cin, cout, taps, seed=seed)"""
+    g = torch.Generator().manual_seed(seed)
+    k = 3 if taps == 9 else 1
+    return torch.randn(cout, cin, k, k, generator=g) * 0.2, torch.randn(cout, generator=g)
+
+
+@functools.lru_cache(maxsize=None)
+def conv_source(kind, seed, N, H, W, C_, p=0.0):
+    """One virtual source of a conv at N x H x W with C_ channels, on the CPU: its raw float32 tensors (unit-scale data, hand-made table),
+    the float64 restatement `v` and its `delta`.  kind: plain | bnact | pool (raw tensors at 2H x 2W) | cat ([bnact C/2 | up2x C/2], the
+    upsampled half at H/2 x W/2) | dz.  The LeakyReLU guard of lrelu_slope holds for the seeds in use.  Computed once; read-only."""
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g) * 2 + 0.5
+    s = dict(kind=kind, C=C_, p=p, dseed=1000 + seed)
+    if kind == "plain":
+        s["z"] = rn(N, H, W, C_)
+        s["v"], s["d"] = s["z"].double(), torch.zeros(N, H, W, C_, dtype=torch.float64)
+        return s
+    if kind == "dz":
+        s["z"], s["dA"], s["tab"] = rn(N, H, W, C_), torch.randn(N, H, W, C_, generator=g), bn_table(C_, seed + 11)
+        s["v"], s["d"] = dz_f64(s["z"], s["dA"], s["tab"], p, s["dseed"])
+        return s
+    ca = C_ // 2 if kind == "cat" else C_
+    up = 2 if kind == "pool" else 1
+    s["z"], s["tab"] = rn(N, up * H, up * W, ca), bn_table(ca, seed + 3)
+    sc, sh = s["tab"][L.BN_SCALE], s["tab"][L.BN_SHIFT]
+    lrelu_slope(s["z"].double(), sc.double(), sh.double())          # the guard
+    if kind == "bnact":
+        s["v"], s["d"] = bnact_f64(s["z"], sc, sh, p, s["dseed"])
+    elif kind == "pool":
+        s["v"], s["d"] = pool_f64(s["z"], sc, sh)
+    else:
+        s["u"] = rn(N, H // 2, W // 2, C_ - ca)
+        s["v"], s["d"] = cat_f64(s["z"], sc, sh, s["u"])
+    return s
+
+
+NARROW_OFF, NARROW_ALL = 0, 1 << 20      # HPFG_OPT_NARROW_DEEP: 0 = 64-wide slices wherever they divide, large = 32-wide slices always
+# A. forward 3x3 on 4 x 16-pixel tiles: kind, p, N, H, W, cin, cout, HPFG_OPT_NARROW_DEEP (None = its default)
+FWD3_CASES = [
+    ("bnact", 0.0, 3, 14, 14, 32, 16, None), ("bnact", 0.3, 3, 6, 20, 64, 4, None), ("bnact", 0.3, 3, 10, 34, 40, 32, None),
+    ("bnact", 0.0, 3, 14, 14, 256, 64, None), ("bnact", 0.3, 3, 10, 34, 64, 64, NARROW_OFF), ("bnact", 0.0, 3, 6, 20, 32, 64, None),
+    ("pool", 0.0, 3, 14, 14, 32, 32, None), ("pool", 0.0, 3, 6, 20, 64, 64, NARROW_OFF), ("pool", 0.0, 3, 10, 34, 40, 16, None),
+    ("cat", 0.0, 3, 14, 14, 64, 16, None), ("cat", 0.0, 3, 6, 20, 64, 64, NARROW_OFF), ("cat", 0.0, 3, 10, 34, 64, 32, None),
+]
+FWD3_PERSISTENT = ("bnact", 0.0, 12, 10, 34, 32, 256, NARROW_ALL)      # 108 tiles on 8 slices of 32 channels: 64 workgroups resident per slice
+# B. dgrad 3x3: gradient source kind, p, N, H, W, layer cin (the output channels), layer cout (K), option, epilogue
+DGRAD3_CASES = [
+    ("dz", 0.0, 3, 14, 14, 16, 32, None, None), ("dz", 0.3, 3, 6, 20, 64, 64, NARROW_OFF, None), ("plain", 0.0, 3, 10, 34, 32, 40, None, None),
+    ("dz", 0.3, 3, 10, 34, 4, 32, None, None), ("dz", 0.0, 3, 14, 14, 64, 32, None, "split"), ("dz", 0.3, 3, 10, 34, 64, 64, None, "stats1"),
+    ("dz", 0.0, 3, 6, 20, 64, 32, None, "pool"), ("plain", 0.0, 3, 14, 14, 32, 64, None, "pool"),
+]
+# C. 1x1: forward from a bnact source (kind, p, N, H, W, cin, cout), dgrad from a plain source (N, H, W, cin, cout), UPBWD dgrad at low sizes
+FWD1_CASES = [("bnact", 0.3, 3, 14, 14, 64, 32), ("bnact", 0.0, 3, 6, 20, 40, 16), ("bnact", 0.0, 3, 10, 34, 128, 64), ("bnact", 0.3, 2, 16, 32, 32, 64)]
+DGRAD1_CASES = [(3, 14, 14, 32, 64), (3, 6, 20, 16, 40), (3, 10, 34, 64, 16), (2, 16, 32, 16, 32)]
+UPBWD_CASES = [(3, 1, 1, 64, 32), (3, 7, 7, 128, 64), (3, 14, 9, 16, 8), (3, 5, 6, 32, 40)]      # N, H, W (low size), cin, cout (= channels of the gradient)
+# D. stage_out: input kind of a 64 -> 64 layer at 3 x 10 x 34 (two 32-wide output slices in the forward conv and in the dgrad)
+STAGE_CASES = [("bnact", 0.3), ("pool", 0.0), ("cat", 0.0)]
+# E. weight gradient: input kind, p, gradient kind, p, N, H, W, cin, cout, taps -- pick_shape's (32, 32), (16, 64), (16, 32), (16, 16)
+WGRAD_CASES = [
+    ("bnact", 0.3, "dz", 0.0, 3, 14, 14, 32, 32, 9), ("pool", 0.0, "dz", 0.3, 3, 10, 34, 16, 64, 9), ("cat", 0.0, "dz", 0.0, 3, 10, 34, 32, 16, 9),
+    ("cat", 0.0, "plain", 0.0, 3, 14, 14, 64, 32, 9), ("plain", 0.0, "dz", 0.3, 3, 14, 14, 16, 32, 9), ("plain", 0.0, "plain", 0.0, 2, 16, 32, 16, 16, 9),
+    ("bnact", 0.0, "plain", 0.0, 3, 10, 34, 40, 64, 9), ("pool", 0.0, "plain", 0.0, 2, 16, 16, 32, 32, 9),
+    ("bnact", 0.3, "plain", 0.0, 3, 14, 14, 64, 32, 1), ("plain", 0.0, "plain", 0.0, 3, 10, 34, 32, 16, 1), ("bnact", 0.0, "plain", 0.0, 2, 16, 32, 16, 16, 1),
+]
+
+
+def case_seed(*case):
+    """a fixed seed per case tuple (the guards were checked for these)"""
+    return sum((i + 1) * int(round(float(x) * 10)) for i, x in enumerate(case) if isinstance(x, (int, float))) % 9973 + sum(map(ord, str(case[0])))
+
+
+def pool_epilogue_seed(case):
+    """seed of pool_epilogue_source for a DGRAD3_CASES entry (offsets for which the arg-max guard passes)"""
+    return case_seed(*case) + (2 if case[0] == "plain" else 1)
+
+
+@functools.lru_cache(maxsize=None)
+def pool_epilogue_source(seed, N, H, W, C_):
+    """The layer below a max-pool whose backward rides in a dgrad epilogue (HpfgConvArgs.bwd_stats == 2): a dz-kind source at 2H x 2W (z, table,
+    dA = the gradient so far) plus `first`, the arg-max of every window of its activated output -- clear of ties by pool_argmax's guard."""
+    s = dict(conv_source("dz", seed, N, 2 * H, 2 * W, C_))
+    a, mag = _act64(s["z"], s["tab"][L.BN_SCALE], s["tab"][L.BN_SHIFT])
+    s["first"] = pool_argmax(a, 3.0 * U24 * mag)
+    return s

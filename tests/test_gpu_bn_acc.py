@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from hpfg_amd import _lib as L
 from hpfg_amd.engine import DescTable
-from tests.helpers import AdHocConv, acc_decode, acc_from_rows, acc_rows_totals, acc_totals, maxerr, nchw, plain_act, stream
+from tests.helpers import AdHocConv, acc_decode, acc_from_rows, acc_rows_totals, acc_totals, lrelu_slope, maxerr, nchw, plain_act, stream
 from tests.test_gpu_fused_bwd import _bnact, _dz
 from tests.test_gpu_kernels import _bn_table
 
@@ -48,11 +48,7 @@ def _ulp32(x):
     return np.spacing(np.abs(np.asarray(x, dtype=np.float64)).astype(np.float32)).astype(np.float64)
 
 
-def _lrelu_slope(z64, sc, sh):
-    """LeakyReLU'(z * scale + shift) as the kernels decide it in fp32; the inputs must keep every decision clear of the rounding of y."""
-    y = z64 * sc + sh
-    assert not bool((y.abs() <= 2.0 ** -22 * torch.maximum((z64 * sc).abs(), sh.abs().expand_as(y))).any()), "test input sits on a LeakyReLU tie"
-    return torch.where(y > 0, torch.ones_like(y), torch.full_like(y, 0.01))
+_lrelu_slope = lrelu_slope      # (the slope with its tie guard lives in tests/helpers.py, next to the float64 restatements that share it)
 
 
 # ---- A. producers --------------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from hpfg_amd import _lib as L
-from tests.helpers import AdHocConv, maxerr, nchw, stream
+from tests.helpers import AdHocConv, materialized_within_delta, maxerr, nchw, stream
 from tests.test_gpu_kernels import _bn_table, _materialize
 from tests.test_gpu_fused_bwd import _bnact
 
@@ -74,6 +74,8 @@ def test_thin_conv_equals_the_chunked_kernel_bitwise(N, H, W, cin, cout, ak, p):
     if stats:
         assert maxerr(part, rpart) < 1e-4 * max(1.0, float(rpart.abs().max()))
     a_in = _materialize(a0, a1, N, H, W, cin)
+    # (the reference input itself -- the act_load4 copy of the producer chain -- against the float64 restatement of that chain, within its delta)
+    materialized_within_delta(a_in, ak, z.cpu(), tab.cpu(), u=ud.cpu() if ak == "cat" else None, p=p, seed=55)
     want = F.conv2d(nchw(a_in), layer.w.cpu(), layer.b.cpu(), padding=1)
     assert maxerr(nchw(out.cpu()), want) < 3e-4 * max(1.0, float(want.abs().max()))
 
@@ -100,6 +102,7 @@ def test_thin_dgrad_of_the_64_to_32_layer_equals_the_chunked_kernel(N, H, W, p):
     got, ref = dgrad(L.MATH_BF16X3), dgrad(L.MATH_BF16X3 | OLD)
     assert torch.equal(got, ref), f"dgrad differs: {maxerr(got.cpu(), ref.cpu())}"
     dz = _materialize(d, None, N, H, W, 32)
+    materialized_within_delta(dz, "dz", zo.cpu(), tabo.cpu(), dA=dA.cpu(), p=p, seed=21)
     xr = torch.zeros(N, 64, H, W, requires_grad=True)
     F.conv2d(xr, layer.w.cpu(), None, padding=1).backward(nchw(dz))
     assert maxerr(nchw(got.cpu()), xr.grad) < 3e-4 * max(1.0, float(xr.grad.abs().max()))

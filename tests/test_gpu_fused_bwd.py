@@ -7,7 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from hpfg_amd import _lib as L
-from tests.helpers import AdHocConv, maxerr, nchw, plain_act, stream
+from tests.helpers import AdHocConv, materialized_within_delta, maxerr, nchw, plain_act, stream
 from tests.test_gpu_kernels import _bn_table, _materialize
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +121,12 @@ def test_fused_bwd_equals_separate_kernels_and_autograd(N, H, W, cin, cout, ak, 
     # ---- plain PyTorch fp32 on the CPU
     a_in = _materialize(xa0, xa1, N, H, W, cin)
     dz = _materialize(gsrc, None, N, H, W, cout)
+    # (both reference operands -- the act_load4 copy of the producer chain -- against the float64 restatements of the chain, within their deltas)
+    materialized_within_delta(a_in, ak, zi.cpu(), tabi.cpu(), u=ud.cpu() if ak == "cat" else None, p=p_in, seed=77)
+    if gk == "dz":
+        materialized_within_delta(dz, "dz", zo.cpu(), tabo.cpu(), dA=dA.cpu(), p=p_out, seed=99)
+    else:
+        materialized_within_delta(dz, "plain", dl.cpu(), tabi.cpu())
     xr = nchw(a_in).requires_grad_(True)
     wr = layer.w.cpu().clone().requires_grad_(True)
     F.conv2d(xr, wr, None, padding=1).backward(nchw(dz))
@@ -176,6 +182,7 @@ def _first_layer_case(N, H, W, cin, streaming):
     dw_ref = layer.wgrad(xa, None, gsrc, N, H, W, math=L.MATH_BF16X3)
     assert maxerr(dw.cpu(), dw_ref.cpu()) < (5e-5 if streaming else 1e-5) * max(1.0, float(dw_ref.abs().max()))      # (exact products vs split-bf16 ones)
     dz = _materialize(gsrc, None, N, H, W, 16)
+    materialized_within_delta(dz, "dz", zo.cpu(), tabo.cpu(), dA=dA.cpu(), p=0.05, seed=3)
     xr = x.cpu().clone()
     wr = layer.w.cpu().clone().requires_grad_(True)
     F.conv2d(xr, wr, None, padding=1).backward(nchw(dz))

@@ -413,3 +413,149 @@ def test_gather_flat_grads_refuses_a_parameter_without_gradient_inside_the_range
     for p in net.parameters():
         p.grad = torch.ones_like(p)
     assert bool((gather_flat_grads(net) == 1.0).all())
+
+
+# ---- float64 restatements of the virtual sources (tests/helpers.py) against torch float64 ops, and the split-bf16 error bound ------------------
+def test_source_restatements_equal_torch_float64_ops():
+    import torch.nn.functional as F
+    from hpfg_amd import _lib as L
+    from tests import helpers as T
+    g = torch.Generator().manual_seed(5)
+    N, H, W, C_ = 2, 6, 10, 8
+    z, tab = torch.randn(N, H, W, C_, generator=g) * 2 + 0.5, T.bn_table(C_, 4)
+    sc, sh = tab[L.BN_SCALE], tab[L.BN_SHIFT]
+    y = z.double() * sc.double() + sh.double()
+    act = F.leaky_relu(y, T.LEAKY32)
+    # bnact: F.leaky_relu, and the keep mask through the oracle's NCHW mask (another indexing path to element pix * C + c)
+    v, d = T.bnact_f64(z, sc, sh)
+    assert torch.equal(v, act) and float(d.min()) > 0
+    v, _ = T.bnact_f64(z, sc, sh, 0.3, 77)
+    keep = torch.from_numpy(rng_ref.keep_mask_nchw(N, C_, H, W, 0.3, 77).astype(np.float64)).permute(0, 2, 3, 1)
+    assert 0.6 < float(keep.mean()) < 0.8 and torch.equal(v, act * (keep / (1.0 - float(np.float32(0.3)))))
+    # pool: F.max_pool2d with indices, its backward
+    pv, _ = T.pool_f64(z, sc, sh)
+    a_ = T.nchw(act).requires_grad_(True)
+    ref, idx = F.max_pool2d(a_, 2, return_indices=True)
+    assert torch.equal(T.nchw(pv), ref)
+    first = T.pool_argmax(act, 3.0 * T.U24 * (y.abs() + 1))          # (a generous delta: this input is clear of ties)
+    yy, xx = torch.meshgrid(torch.arange(H // 2), torch.arange(W // 2), indexing="ij")
+    flat = (2 * yy[None, :, :, None] + first // 2) * W + 2 * xx[None, :, :, None] + first % 2
+    assert torch.equal(T.nchw(flat), idx)
+    dP = torch.randn(N, H // 2, W // 2, C_, generator=g).double()
+    ref.backward(T.nchw(dP))
+    assert torch.equal(T.nchw(T.pool_scatter_f64(dP, first)), a_.grad)
+    tie = torch.zeros(1, 2, 2, 1, dtype=torch.float64)
+    assert int(T.pool_argmax(tie)) == 0                               # first maximum in row-major order
+    with pytest.raises(AssertionError, match="max-pool tie"):
+        T.pool_argmax(tie, torch.full_like(tie, 1e-9))
+    with pytest.raises(AssertionError, match="LeakyReLU tie"):
+        T.lrelu_slope(torch.zeros(1, dtype=torch.float64), torch.ones(1, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))
+    # up2x / upbwd: F.interpolate(align_corners=True) and its autograd.  The float32 weight law moves a weight by at most 2 u (index): the
+    # values by 2 * 2 u (h + w) max|u| on an h x w source
+    for h, w in [(1, 1), (3, 10), (7, 7), (5, 17)]:
+        u = (torch.randn(N, h, w, C_, generator=g) * 2).double()
+        un = T.nchw(u).requires_grad_(True)
+        ref = F.interpolate(un, scale_factor=2, mode="bilinear", align_corners=True)
+        up, dlt = T.up2x_f64(u)
+        tol = 4.0 * T.U24 * (h + w) * float(u.abs().max())
+        assert float((T.nchw(up) - ref).abs().max()) <= tol and up.shape == (N, 2 * h, 2 * w, C_) and float(dlt.max()) <= (6.1 + 4 * (h + w)) * T.U24 * float(u.abs().max())
+        gup = torch.randn(N, 2 * h, 2 * w, C_, generator=g).double()
+        ref.backward(T.nchw(gup))
+        gb, _ = T.upbwd_f64(gup)
+        assert float((T.nchw(gb) - un.grad).abs().max()) <= 4.0 * T.U24 * (h + w) * 9 * float(gup.abs().max())      # (up to 9 taps of a 3 x 3 footprint carry weight)
+        assert abs(float((up * gup).sum() - (u * gb).sum())) <= 1e-12 * float((up.abs() * gup.abs()).sum())            # the exact transpose
+    # cat: the two halves side by side
+    u = torch.randn(N, H // 2, W // 2, 4, generator=g)
+    cv, cd = T.cat_f64(z, sc, sh, u)
+    assert torch.equal(cv[..., :C_], act) and torch.equal(cv[..., C_:], T.up2x_f64(u)[0]) and cd.shape == cv.shape
+    # dz: F.conv2d autograd through BatchNorm (train mode) + LeakyReLU + Dropout -- dZ = k1 g + k2 z + k3 with the table rows of its batch statistics
+    p, seed, eps = 0.3, 123, 1e-5
+    gamma, beta = torch.randn(C_, generator=g).double(), torch.randn(C_, generator=g).double()
+    zr = T.nchw(z.double()).requires_grad_(True)
+    yb = F.batch_norm(zr, None, None, gamma, beta, training=True, eps=eps)
+    a = F.leaky_relu(yb, T.LEAKY32) * T.nchw(T.keep_f64((N, H, W, C_), p, seed))
+    a.retain_grad()
+    w = torch.randn(5, C_, 3, 3, generator=g).double()
+    F.conv2d(a, w, None, padding=1).backward(torch.randn(N, 5, H, W, generator=g).double())
+    mean, var = z.double().mean((0, 1, 2)), z.double().var((0, 1, 2), unbiased=False)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    t64 = torch.zeros(L.BN_ROWS, C_, dtype=torch.float64)
+    t64[L.BN_SCALE] = gamma * rstd
+    t64[L.BN_SHIFT] = beta - mean * t64[L.BN_SCALE]
+    dA = a.grad.permute(0, 2, 3, 1)
+    gg = dA * T.keep_f64((N, H, W, C_), p, seed) * torch.where(T.lrelu_slope(z.double(), t64[L.BN_SCALE], t64[L.BN_SHIFT]) == 1.0, 1.0, T.LEAKY32)
+    m1, m2 = gg.mean((0, 1, 2)), (gg * (z.double() - mean) * rstd).mean((0, 1, 2))
+    t64[L.BN_K1] = gamma * rstd
+    t64[L.BN_K2] = -(gamma * rstd * rstd) * m2
+    t64[L.BN_K3] = gamma * rstd * (mean * rstd * m2 - m1)
+    dzv, dzd = T.dz_f64(z, dA, t64, p, seed)
+    assert float((T.nchw(dzv) - zr.grad).abs().max()) <= 1e-12 * float(zr.grad.abs().max()) and float(dzd.min()) >= 0
+
+
+def _conv_case_checks():
+    """(tag, group, float64 reference, bound, emulated result) of every case of tests/test_gpu_conv_sources.py, from its CPU inputs"""
+    from oracle import bf16x3_ref
+    from tests import helpers as T
+
+    def emu(kind, a, w, b=None, g=None):
+        pad = w.shape[-1] // 2
+        with bf16x3_ref.math_mode("bf16x3"):
+            if kind == "conv":
+                return bf16x3_ref.conv2d(T.nchw(a).float(), w, b, padding=pad).permute(0, 2, 3, 1).double()
+            xr = (T.nchw(a).float() if a is not None else torch.zeros(g.shape[0], w.shape[1], g.shape[1], g.shape[2])).requires_grad_(True)
+            wr = w.clone().requires_grad_(True)
+            bf16x3_ref.conv2d(xr, wr, None, padding=pad).backward(T.nchw(g).float())
+            return xr.grad.permute(0, 2, 3, 1).double() if kind == "dgrad" else wr.grad.double()
+
+    for c in T.FWD3_CASES + [T.FWD3_PERSISTENT] + [k + (None,) for k in T.FWD1_CASES]:
+        kind, p, N, H, W, cin, cout = c[:7]
+        taps = 9 if len(c) == 8 and c in T.FWD3_CASES + [T.FWD3_PERSISTENT] else 1
+        s = T.conv_source(kind, T.case_seed(*c), N, H, W, cin, p)
+        w, b = T.adhoc_weights(cin, cout, taps, T.case_seed(*c))
+        ref, bound = T.conv_ref_bound(s["v"], s["d"], w, b)
+        yield f"fwd{taps} {c}", "A" if taps == 9 else "C", ref, bound, emu("conv", s["v"], w, b)
+    for c in T.DGRAD3_CASES + [("plain", 0.0) + k + (None, None) for k in T.DGRAD1_CASES]:
+        kind, p, N, H, W, cin, cout = c[:7]
+        taps = 9 if c in T.DGRAD3_CASES else 1
+        s = T.conv_source(kind, T.case_seed(*c), N, H, W, cout, p)
+        w, _ = T.adhoc_weights(cin, cout, taps, T.case_seed(*c))
+        ref, bound = T.dgrad_ref_bound(s["v"], s["d"], w)
+        if c[-1] == "pool":
+            T.pool_epilogue_source(T.pool_epilogue_seed(c), N, H, W, cin)          # (its arg-max guard)
+        yield f"dgrad{taps} {c}", "B" if taps == 9 else "C", ref, bound, emu("dgrad", None, w, g=s["v"])
+    for c in T.WGRAD_CASES:
+        ak, pa, gk, pg, N, H, W, cin, cout, taps = c
+        sa = T.conv_source(ak, T.case_seed(*c), N, H, W, cin, pa)
+        sg = T.conv_source(gk, T.case_seed(*c) + 1, N, H, W, cout, pg)
+        w, _ = T.adhoc_weights(cin, cout, taps, T.case_seed(*c))
+        ref, bound = T.wgrad_ref_bound(sa["v"], sa["d"], sg["v"], sg["d"], w.shape)
+        yield f"wgrad {c}", "E", ref, bound, emu("wgrad", sa["v"], w, g=sg["v"])
+    for c in T.UPBWD_CASES:
+        N, H, W, cin, cout = c
+        v, d = T.upbwd_f64(torch.randn(N, 2 * H, 2 * W, cout, generator=torch.Generator().manual_seed(T.case_seed(*c))))
+        w, _ = T.adhoc_weights(cin, cout, 1, T.case_seed(*c))
+        ref, bound = T.dgrad_ref_bound(v, d, w)
+        yield f"upbwd dgrad {c}", "C", ref, bound, emu("dgrad", None, w, g=v)
+    for kind, p in T.STAGE_CASES:
+        c = (kind, p, 3, 10, 34, 64, 64)
+        si, sg = T.conv_source(kind, T.case_seed(*c), 3, 10, 34, 64, p), T.conv_source("dz", T.case_seed(*c) + 1, 3, 10, 34, 64, 0.3)
+        w, b = T.adhoc_weights(64, 64, 9, T.case_seed(*c))
+        ref, bound = T.conv_ref_bound(si["v"], si["d"], w, b)
+        yield f"stage fwd {c}", "D", ref, bound, emu("conv", si["v"], w, b)
+        ref, bound = T.dgrad_ref_bound(sg["v"], sg["d"], w)
+        yield f"stage dgrad {c}", "D", ref, bound, emu("dgrad", None, w, g=sg["v"])
+        ref, bound = T.wgrad_ref_bound(si["v"], si["d"], sg["v"], sg["d"], w.shape)
+        yield f"stage wgrad {c}", "D", ref, bound, emu("wgrad", si["v"], w, g=sg["v"])
+
+
+def test_split_product_emulation_stays_within_the_bound_on_every_case():
+    """The condition on the inputs of tests/test_gpu_conv_sources.py: oracle.bf16x3_ref.conv2d -- the three kept products with fp32 accumulation
+    -- stays within the bound of tests/helpers.py against the float64 convolution for every case (and every guard of the inputs passes)."""
+    worst = {}
+    for tag, group, ref, bound, got in _conv_case_checks():
+        assert bool(torch.isfinite(ref).all()) and float(bound.min()) > 0, tag
+        r = float(((got - ref).abs() / bound).max())
+        worst[group] = max(worst.get(group, 0.0), r)
+        assert r <= 1.0, f"{tag}: the emulation is {r:.3g} x the bound off the float64 result"
+    for group in sorted(worst):
+        print(f"[conv_sources] {group} (CPU emulation): largest error / bound = {worst[group]:.3g}")
