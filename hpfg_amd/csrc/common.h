@@ -180,21 +180,26 @@ __device__ __forceinline__ void hpfg_dz_rows_to_lds(const HpfgAct& a, float* t, 
     for (int r = 0; r < 5; ++r) t[r * cmax + c] = v[r];
   }
 }
-// scale / shift of the C channels of a BatchNorm'd source -> t[0 .. C) and t[cmax .. cmax + C) (LDS; all NTHR threads call, the caller syncs)
-__device__ __forceinline__ void hpfg_bn_rows_to_lds(const HpfgAct& a, float* t, int cmax, int tid, int nthr) {
-  for (int c = tid; c < a.C; c += nthr) {
-    float sc, sh;
-    if (a.bn_acc) {
-      const int cc = a.bn_coff + c;
-      const float ga = a.bn_gamma[cc], be = a.bn_beta[cc];      // (requested WITH the accumulator words: one round trip, see hpfg_dz_rows_to_lds)
-      double s1, s2;
-      hpfg_acc_read2(a.bn_acc, a.bn_stride, a.bn_shards, cc, s1, s2, ga + be);
-      const HpfgBnCoef q = hpfg_bn_coef(s1, s2, (double)a.bn_count, a.bn_eps, ga, be);
-      sc = q.scale;
-      sh = q.shift;
-    } else {
-      sc = a.bn[a.bn_coff + HPFG_BN_SCALE * a.bn_stride + c];
-      sh = a.bn[a.bn_coff + HPFG_BN_SHIFT * a.bn_stride + c];
+// scale / shift of a BatchNorm'd source -> t[0 .. nch) and t[cmax .. cmax + nch), zeros at and past its C channels (LDS; all NTHR threads
+// call, the caller syncs): from the table rows, or (ACC and a.bn_acc) derived here from the producer's sum accumulators.  ACC = false: the
+// backward kernels, which read the table the forward pass left whatever a.bn_acc says (the accumulators are spent by then).
+template <bool ACC = true>
+__device__ __forceinline__ void hpfg_bn_rows_to_lds(const HpfgAct& a, float* t, int cmax, int nch, int tid, int nthr) {
+  for (int c = tid; c < nch; c += nthr) {
+    float sc = 0.f, sh = 0.f;
+    if (c < a.C) {
+      if (ACC && a.bn_acc) {
+        const int cc = a.bn_coff + c;
+        const float ga = a.bn_gamma[cc], be = a.bn_beta[cc];      // (requested WITH the accumulator words: one round trip, see hpfg_dz_rows_to_lds)
+        double s1, s2;
+        hpfg_acc_read2(a.bn_acc, a.bn_stride, a.bn_shards, cc, s1, s2, ga + be);
+        const HpfgBnCoef q = hpfg_bn_coef(s1, s2, (double)a.bn_count, a.bn_eps, ga, be);
+        sc = q.scale;
+        sh = q.shift;
+      } else {
+        sc = a.bn[a.bn_coff + HPFG_BN_SCALE * a.bn_stride + c];
+        sh = a.bn[a.bn_coff + HPFG_BN_SHIFT * a.bn_stride + c];
+      }
     }
     t[c] = sc;
     t[cmax + c] = sh;

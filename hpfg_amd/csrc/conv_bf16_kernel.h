@@ -44,8 +44,6 @@ struct Cfg {
   static_assert(TAPS == 1 || NLD + 2 <= KSTEPS, "stage pipeline must fit into the k-steps of a chunk");
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }   // v_med3_i32
-
 // per-thread, tile-invariant description of staging piece i: local pixel (ly, lx) and LDS byte offset
 struct Piece {
   int ly, lx, lds, ok;
@@ -284,26 +282,18 @@ __device__ __forceinline__ void conv16_flush_stats(const HpfgConvArgs& p, f32x4 
   ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BL, AH, ACC, 0, 0, 0); \
   ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BH, AL, ACC, 0, 0, 0);
 
-// Concat loader (KIND == CAT), upsampled half: the bilinear x2 taps of a tile come from a (TH/2+3) x (TW/2+3) patch of the
-// low-resolution 1x1-conv output.  That patch is fetched ONCE per chunk (at most one 8-channel piece per thread, two float4:
-// prefetched a chunk ahead like the cheap loaders), parked in LDS as fp32, and every output piece interpolates its four taps
-// from LDS -- instead of 8 float4 global loads per output piece (24 per thread and chunk), whose registers forced a
-// two-k-step pipeline that exposed one memory latency per piece.  Skip-half chunks are plain BN + LeakyReLU pieces.
+// Concat loader (KIND == CAT): the upsampled half goes through the LDS patch of stage.h, one chunk of KC channels at a time (the patch piece
+// of a thread is prefetched a chunk ahead like the cheap loaders).  Skip-half chunks are plain BN + LeakyReLU pieces.
 template <class C>
 struct UpGeo {
-  static constexpr int SH = C::TH / 2 + 3, SW = C::TW / 2 + 3;
-  static constexpr int NPIECE = SH * SW * C::NG;
-  static constexpr int BYTES = SH * SW * C::KC * 4;
+  using P = UpPatch<C::TH, C::TW>;
+  static constexpr int SW = P::SW;
+  static constexpr int NPIECE = P::SH * P::SW * C::NG;
+  static constexpr int BYTES = P::SH * P::SW * C::KC * 4;
   static_assert(NPIECE <= 256, "one source piece per thread");
 };
 template <int KIND>
 constexpr int eff_nr() { return KIND == HPFG_KIND_CAT ? 2 : RawCount<KIND>::N; }   // float4 loads in flight per piece
-
-// first low-res row / column a tile (with its halo) touches: source index of output coordinate max(o0, 0)
-__device__ __forceinline__ int up_base(int o0, int L) {
-  const float r = L > 1 ? (float)(L - 1) / (float)(2 * L - 1) : 0.f;
-  return (int)(r * (float)(o0 < 0 ? 0 : o0));
-}
 
 // Resident workgroups per CU the kernel is compiled for.  The thin 16x16-tile layers behind a cheap loader are HBM-bound: three
 // workgroups per CU keep more tile loads in flight; everything else needs the registers of a two-per-CU budget.
@@ -311,22 +301,6 @@ template <class C, int KIND>
 constexpr int wg_per_cu() {
   return (C::KSTEPS == 5 && C::NI == 1 && RawCount<KIND>::N <= 2) ? 3 : 2;      // (the concat kernel would spill at 168 VGPRs)
 }
-
-// Diagnostics build only (make TRACE=1 -> libhpfg_hip_trace.so, tools/trace_conv.py): with math bit 0x2000 wave 0 of every
-// workgroup writes (id << 56 | s_memtime) stamps to stat_partials + 256 * blockIdx.x (u64), which the tool sizes accordingly.
-#ifdef HPFG_TRACE
-#define HPFG_TR(ID)                                                                                        \
-  if (tr_on && tr_i < 255) {                                                                               \
-    tr_buf[tr_i++] = ((unsigned long long)(ID) << 56) | (__builtin_amdgcn_s_memtime() & 0xffffffffffffffull); \
-  }
-#define HPFG_TR_REAL(ID)                                                                                   \
-  if (tr_on && tr_i < 255) {                                                                               \
-    tr_buf[tr_i++] = ((unsigned long long)(ID) << 56) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffffffffull); \
-  }
-#else
-#define HPFG_TR(ID)
-#define HPFG_TR_REAL(ID)
-#endif
 
 // BWD: the dgrad variant whose epilogue also produces the BatchNorm-backward sums of the layer below (p.bwd_stats); a separate
 // instantiation so that the plain kernels keep their register budget.
@@ -396,16 +370,9 @@ __global__ __launch_bounds__(256, (wg_per_cu<C, KIND>())) void conv_bf16x3_kerne
   const int nt0 = (cb * C::WN + wn) * C::NI;
   const bf16x8* wpk = reinterpret_cast<const bf16x8*>(p.wpk);
 
-  // XCD-aware work mapping: workgroups are dealt round-robin over the 8 XCDs (b % 8 names the XCD group), each XCD has its own
-  // L2.  Give every XCD group a CONTIGUOUS range of tiles (row-major inside an image) so that tiles sharing a halo are read
-  // through the same L2; inside a group, workgroup j takes tiles j, j + G, j + 2G, ... of the range.  (Speed only: any mapping
-  // is correct.)
-  const int nx = gridDim.x >= 8 ? 8 : 1;
-  const int xg = (int)blockIdx.x % nx, xj = (int)blockIdx.x / nx;
-  const int per_x = (nwork + nx - 1) / nx;                 // tiles per XCD group
-  const int wend = (xg + 1) * per_x < nwork ? (xg + 1) * per_x : nwork;
-  const int G = ((int)gridDim.x - xg + nx - 1) / nx;       // workgroups in this group
-  int w = xg * per_x + xj;
+  const TileWalk tw = tile_walk(nwork, gridDim.x >= 8 ? 8 : 1);      // this workgroup takes tiles w, w + G, w + 2G, ... < wend
+  const int wend = tw.wend, G = tw.step;
+  int w = tw.w;
   if (w >= wend) {   // no tile for this workgroup: its BatchNorm partial row must still be defined
     if (p.stat_partials && threadIdx.x < 2 * C::BN) {
       const int co = cb * C::BN + (int)threadIdx.x % C::BN;
@@ -442,7 +409,7 @@ __global__ __launch_bounds__(256, (wg_per_cu<C, KIND>())) void conv_bf16x3_kerne
       issue_piece<KIND>(raw0[i], p.a0, p.a1, cx0, n, clampi(gy, 0, H - 1), clampi(gx, 0, W - 1), c0c, ok);
     }
     if constexpr (TABK) {
-      fill_tables_lds<KIND>(p.a0, ldsBN, tid, 256);
+      fill_tables_lds<KIND>(p.a0, ldsBN, p.a0.C, tid, 256);
       __syncthreads();
       load_tables_lds<KIND>(tab, ldsBN, p.a0, c0c);
     } else {
@@ -518,15 +485,10 @@ __global__ __launch_bounds__(256, (wg_per_cu<C, KIND>())) void conv_bf16x3_kerne
       f32x4 rawU[2];
       int sy_base = 0, sx_base = 0;
       if (CATK && up_next) {
-        using UG = UpGeo<C>;
         sy_base = up_base(nty - 1, p.a1.Hs);
         sx_base = up_base(ntx - 1, p.a1.Ws);
-        const int pix = tid / C::NG;
-        const int sy = clampi(sy_base + pix / UG::SW, 0, p.a1.Hs - 1), sx = clampi(sx_base + pix % UG::SW, 0, p.a1.Ws - 1);
         const int cu = (c0n < cin_total ? c0n : p.a0.C) - p.a0.C;                 // channel inside the upsampled tensor
-        const int off = ((nn * p.a1.Hs + sy) * p.a1.Ws + sx) * p.a1.pstride + cu;
-        rawU[0] = ld4(p.a1.z, off);
-        rawU[1] = ld4(p.a1.z, off + 4);
+        up_patch_issue<UpGeo<C>::SW>(rawU, p.a1, nn, sy_base, sx_base, tid / C::NG, cu);
       } else if (DEEP) {
 #pragma unroll
         for (int i = 0; i < C::NLD; ++i) {
@@ -588,35 +550,14 @@ __global__ __launch_bounds__(256, (wg_per_cu<C, KIND>())) void conv_bf16x3_kerne
       if (CATK && up_next) {
         using UG = UpGeo<C>;
         // park the low-res patch (fp32, [pixel][KC channels]), then every output piece blends its four taps from LDS
-        if (tid < UG::NPIECE) {
-          float* d = ldsU + (tid / C::NG) * C::KC + g8;
-          *reinterpret_cast<f32x4*>(d) = rawU[0];
-          *reinterpret_cast<f32x4*>(d + 4) = rawU[1];
-        }
+        if (tid < UG::NPIECE) up_patch_park<C::KC>(ldsU, rawU, tid / C::NG, g8);
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < C::NLD; ++i) {
           const int gy = nty + pc[i].ly, gx = ntx + pc[i].lx;
           const bool ok = pc[i].ok && chvn && gy >= 0 && gy < H && gx >= 0 && gx < W;
-          int y0, y1, x0, x1;
-          float wy1, wx1;
-          up_coord(clampi(gy, 0, H - 1), p.a1.Hs, y0, y1, wy1);
-          up_coord(clampi(gx, 0, W - 1), p.a1.Ws, x0, x1, wx1);
-          const float wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-          const float* r0 = ldsU + ((y0 - sy_base) * UG::SW) * C::KC + g8;
-          const float* r1 = ldsU + ((y1 - sy_base) * UG::SW) * C::KC + g8;
-          const int o0 = (x0 - sx_base) * C::KC, o1 = (x1 - sx_base) * C::KC;
-          const f32x4 a00 = *reinterpret_cast<const f32x4*>(r0 + o0), b00 = *reinterpret_cast<const f32x4*>(r0 + o0 + 4);
-          const f32x4 a01 = *reinterpret_cast<const f32x4*>(r0 + o1), b01 = *reinterpret_cast<const f32x4*>(r0 + o1 + 4);
-          const f32x4 a10 = *reinterpret_cast<const f32x4*>(r1 + o0), b10 = *reinterpret_cast<const f32x4*>(r1 + o0 + 4);
-          const f32x4 a11 = *reinterpret_cast<const f32x4*>(r1 + o1), b11 = *reinterpret_cast<const f32x4*>(r1 + o1 + 4);
-          f32x4 v0 = wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11);     // same expression order as finish_piece<CAT>
-          f32x4 v1 = wy0 * (wx0 * b00 + wx1 * b01) + wy1 * (wx0 * b10 + wx1 * b11);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            v0[j] = ok ? v0[j] : 0.f;
-            v1[j] = ok ? v1[j] : 0.f;
-          }
+          f32x4 v0, v1;
+          up_blend<C::KC, UG::SW>(v0, v1, ldsU, p.a1, clampi(gy, 0, H - 1), clampi(gx, 0, W - 1), sy_base, sx_base, g8, ok);
           store_piece<C, HPFG_KIND_PLAIN, SIDE>(nxt, pc[i], v0, v1, &p, dzw, nn, gy, gx, c0c, ok);
         }
       } else if (DEEP) {      // also on the last item: the pieces land in the unused buffer
@@ -708,7 +649,7 @@ __global__ __launch_bounds__(256) void conv1x1_bf16x3_kernel(HpfgConvArgs p, int
   const bf16x8* wpk = reinterpret_cast<const bf16x8*>(p.wpk);
   Tab tab;
   if constexpr (TABK) {
-    fill_tables_lds<KIND>(p.a0, ldsBN, tid, 256);
+    fill_tables_lds<KIND>(p.a0, ldsBN, p.a0.C, tid, 256);
     __syncthreads();
   }
   if constexpr (UPB) {      // tap lists of this tile's rows and columns: HPFG_UPB_TAPS entries each, unused ones repeat the last index with weight 0

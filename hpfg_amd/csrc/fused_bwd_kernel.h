@@ -33,37 +33,29 @@
 // sums of the layer below).
 #pragma once
 #include <type_traits>
-#include "conv_bf16_kernel.h"
+#include "tile16.h"
 
 namespace hpfg_fused {
 
-using namespace hpfg_stage;
+using namespace hpfg_tile16;
 using hpfg_conv16::Cfg;
-using hpfg_conv16::clampi;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int T = 16, HP = 18, RS = 18;                 // tile edge, halo tile edge, dZ row stride in slots
-constexpr int DSLOT = (HP * HP + 15) / 16 * 16;         // 336
-constexpr int DPL = DSLOT * 32;                         // bytes per hi / lo plane of one 16-channel chunk of the dZ tile: 32 bytes per pixel slot
-constexpr int APL = T * T * 32;                         // ... of the A tile
-constexpr int DCH = 2 * DPL, ACH = 2 * APL;             // one 16-channel chunk = (hi, lo)
-constexpr int USH = T / 2 + 3, USW = T / 2 + 3;         // low-resolution source patch of an upsampled chunk of the (interior) input tile
-constexpr int UBYTES = USH * USW * 16 * 4;              // fp32, [pixel][16 ch]
+constexpr int DPL = PL, DCH = CH;                       // the dZ tile: the halo-tile layout of tile16.h
+constexpr int APL = T * T * 32;                         // bytes per hi / lo plane of one 16-channel chunk of the A tile (interior only)
+constexpr int ACH = 2 * APL;                            // one 16-channel chunk = (hi, lo)
 
 // NW waves per workgroup: staging pieces (8 channels of one pixel) per thread and 16-channel chunk, pixel tiles per wave in dgrad
 template <int NW>
 struct Split {
   static constexpr int NTH = 64 * NW;
-  static constexpr int ND = (HP * HP * 2 + NTH - 1) / NTH, NA = T * T * 2 / NTH, MI = 16 / NW;
+  static constexpr int ND = halo_pieces<NTH>(), NA = T * T * 2 / NTH, MI = 16 / NW;
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
 };
 
 template <int CI, int CO, int AK, int GK, int NW, bool BWD, int BMAX = 48>
-struct Geo {
-  static constexpr bool CATK = AK == HPFG_KIND_CAT;
-  static constexpr int AK0 = CATK ? HPFG_KIND_BNACT : AK;          // loader kind of the chunks read through xa0 (concat: the skip half)
-  static constexpr int NA0 = CATK ? CI / 2 : CI, NA1 = CATK ? CI / 2 : 0;
+struct Geo : Halves<CI, AK> {
+  using Halves<CI, AK>::NA0;
+  using Halves<CI, AK>::NA1;
   static constexpr int TABD = GK == HPFG_KIND_DZ ? 5 * 16 * CO * 4 : 0;      // sc, sh, k1, k2, k3 rows of the dZ layer
   static constexpr int TABA = 2 * 16 * NA0 * 4;                              // sc, sh rows of the input's producer
   static constexpr int STAT = 2 * NW * 16 * CI * 4;
@@ -77,12 +69,6 @@ struct Geo {
                        OFF_Z = OFF_B + BFR, OFF_U = OFF_Z + ZL;
   static constexpr int LDS = OFF_U + NA1 * UBYTES;
 };
-
-__device__ __forceinline__ bf16x8 tr8(const unsigned char* p0, const unsigned char* p1) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p0));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p1));
-  return __builtin_bit_cast(bf16x8, (s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}));
-}
 
 // CI = CinPad / 16, CO = CoutPad / 16 of the layer; AK / GK = loader kinds of the layer input and of dZ; NW = waves per workgroup (8 for the
 // wider layers: per-thread staging registers and accumulators halve, which is what lets a whole tile be prefetched); WGS = workgroups per CU
@@ -104,14 +90,13 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
   const bf16x8* ldsB = reinterpret_cast<const bf16x8*>(lds + G::OFF_B);
   unsigned char* ldsZ = lds + G::OFF_Z;
   float* ldsU = reinterpret_cast<float*>(lds + G::OFF_U);
-  static_assert(NA1 == 0 || USH * USW * 2 <= NTH, "one source piece of the upsampled half per thread");
+  static_assert(NA1 == 0 || UP::SH * UP::SW * 2 <= NTH, "one source piece of the upsampled half per thread");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int H = p.d.H, W = p.d.W;
   const int ntiles = tiles_x * tiles_y, nwork = ntiles * p.d.N;
   const HpfgAct none = {};
   const HpfgAct& aD = p.d.a0;
-  HpfgAct aS = p.xa0;                                    // (the skip half of a concat carries no dropout: model/unet.py:57 concatenates block outputs)
-  if (G::CATK) aS.drop_p = 0.f;
+  const HpfgAct aS = skip_source<G::CATK>(p.xa0);
   const ActCtx cxg = make_ctx(aD), cxa = make_ctx(aS);
 #ifdef HPFG_TRACE      // diagnostics build (make TRACE=1, tools/trace_fused.py): thread 0 stamps s_memtime at the phase boundaries into d.bias
   const bool tr_on = (p.d.math & 0x2000) && tid == 0;
@@ -123,11 +108,8 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
   const int gsel = tid & 1;                              // this thread's 8-channel group inside a 16-channel chunk (256 % 2 == 0)
 
   // ---- per-channel tables -> LDS, once (rows: scale, shift [, k1, k2, k3])
-  if (GK == HPFG_KIND_DZ) hpfg_dz_rows_to_lds(aD, tabD, 16 * CO, 16 * CO, tid, NTH);      // (table rows, or k1 .. k3 from the backward sum accumulators)
-  for (int i = tid; i < 2 * 16 * NA0 && AK0 != HPFG_KIND_PLAIN; i += NTH) {
-    const int r = i / (16 * NA0), ch = i % (16 * NA0);
-    tabA[i] = ch < aS.C ? aS.bn[aS.bn_coff + (r == 0 ? HPFG_BN_SCALE : HPFG_BN_SHIFT) * aS.bn_stride + ch] : 0.f;
-  }
+  if (GK == HPFG_KIND_DZ) fill_tables_lds<GK, 16 * CO>(aD, tabD, 16 * CO, tid, NTH);      // (table rows, or k1 .. k3 from the backward sum accumulators)
+  fill_tables_lds<AK0, 16 * NA0, false>(aS, tabA, 16 * NA0, tid, NTH);      // (from the table the forward pass left, not its spent accumulators)
 
   // ---- wgrad work split: pair (i, j) = (input tile, output tile); with fewer than 4 pairs the 9 taps are dealt over the waves
   constexpr int NIJ = CI * CO;
@@ -142,39 +124,22 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
     for (int t = 0; t < NT; ++t) accw[a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int wt0 = NIJ >= NW ? 0 : wave / NIJ;
 
-  // ---- dgrad fragment offsets (conv_bf16_kernel.h): pixel tile m of this wave, taps 2s / 2s+1 by k-group
-  const int kg = lane >> 4, gl = kg & 1;
+  // ---- dgrad fragment offsets: pixel tile m of this wave, taps 2s / 2s+1 by k-group
+  const int kg = lane >> 4;
   int aoff[MI], toff[5];
-#pragma unroll
-  for (int m = 0; m < MI; ++m) {
-    const int pxl = (wave * MI + m) * 16 + (lane & 15);
-    aoff[m] = ((pxl / T) * RS + (pxl % T)) * 32 + gl * 16;
-  }
-#pragma unroll
-  for (int s = 0; s < 5; ++s) {
-    int tap = 2 * s + (kg >> 1);
-    tap = tap > 8 ? 8 : tap;                             // tap 9 re-reads tap 8 against zero weights
-    toff[s] = ((tap / 3) * RS + (tap % 3)) * 32;
-  }
+  frag_offsets<MI>(aoff, toff, wave, lane);
   // ---- wgrad transposing-read offsets: k-group kg covers pixels x = 4 kg .. 4 kg + 3 of two tile rows; lane 4 q + pp of the group
   // addresses pixel q, channels 4 pp .. 4 pp + 3
   const int q4 = (lane & 15) >> 2, pp = lane & 3;
   const int trA = (4 * kg + q4) * 32 + pp * 8, trD = trA;
 
-  // ---- dgrad weight fragments do not depend on the tile: they stay in registers for the whole kernel when they are few (one 16-channel
-  // tile in and out), otherwise in LDS -- streamed from L2 per tile they stalled every other k-step (8 waves x 40 KB per tile, each k-step
-  // pair shorter than the L2 latency)
+  // ---- dgrad weight fragments: in registers when they are few (one 16-channel tile in and out), otherwise in LDS (tile16.h)
   constexpr int KS = G::KS;
   constexpr int PB = G::BREG && !NODG ? KS : 0;
   const int ntn = p.d.CoutPad / 16;                      // dgrad output-channel tiles = CI
   const bf16x8* wpk = reinterpret_cast<const bf16x8*>(p.d.wpk);
   bf16x8 pbh[PB > 0 ? PB : 1][CI], pbl[PB > 0 ? PB : 1][CI];
-#pragma unroll
-  for (int k = 0; k < PB; ++k) hpfg_conv16::load_b<C>(pbh[k], pbl[k], wpk, k, ntn, 0, lane);
-  if (!G::BREG && !NODG) {
-    bf16x8* dst = reinterpret_cast<bf16x8*>(lds + G::OFF_B);
-    for (int i = tid; i < KS * CI * 2 * 64; i += NTH) dst[i] = wpk[i];
-  }
+  resident_weights<C, PB, !G::BREG && !NODG>(pbh, pbl, wpk, ntn, reinterpret_cast<bf16x8*>(lds + G::OFF_B), KS * CI * 2 * 64, tid, NTH);
 
   f32x4 s1[CI], s2[CI];
 #pragma unroll
@@ -185,17 +150,13 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
   ActCtx bcx = {};
   if (BWD) bcx = make_ctx(p.d.bwd_of);
 
-  // ---- XCD-aware work mapping (conv_bf16_kernel.h): every XCD group walks a contiguous range of tiles
-  const int nx = gridDim.x >= 8 ? 8 : 1;
-  const int xg = (int)blockIdx.x % nx, xj = (int)blockIdx.x / nx;
-  const int per_x = (nwork + nx - 1) / nx;
-  const int wend = (xg + 1) * per_x < nwork ? (xg + 1) * per_x : nwork;
-  const int GS = ((int)gridDim.x - xg + nx - 1) / nx;    // workgroups of this group = tile stride
+  const TileWalk tw = tile_walk(nwork, gridDim.x >= 8 ? 8 : 1);      // every XCD group walks a contiguous range of tiles
+  const int wend = tw.wend, GS = tw.step;
 
   RawPiece<GK> rawD[CO][ND];
   RawPiece<AK0> rawA0[NA0][NA];
   f32x4 rawU[NA1 > 0 ? NA1 : 1][2];      // concat: the low-res source patch of the tile (one 8-channel piece per thread and upsampled chunk),
-                                         // parked in LDS and blended from there (conv_bf16_kernel.h) -- 8 float4 loads per output piece otherwise
+                                         // parked in LDS and blended from there (stage.h) -- 8 float4 loads per output piece otherwise
 
   // loads of one tile.  EARLY: dZ and the first PFA input chunks (a tile ahead); !EARLY: the remaining input chunks.  live == false: the
   // workgroup has no further tile -- every lane then reads pixel (0, 0, 0), one cache line, and nothing is made of it.
@@ -205,14 +166,7 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
 #pragma unroll
       for (int c = 0; c < CO; ++c) {
         const int c0 = c * 16 + gsel * 8;
-        const bool chv = c0 < aD.C;
-#pragma unroll
-        for (int i = 0; i < ND; ++i) {
-          const int idx = tid + i * NTH, pix = idx >> 1;
-          const int gy = ty0 + pix / HP - 1, gx = tx0 + pix % HP - 1;
-          const bool ok = live && idx < HP * HP * 2 && chv && gy >= 0 && gy < H && gx >= 0 && gx < W;
-          issue_piece<GK>(rawD[c][i], aD, none, cxg, n, live ? clampi(gy, 0, H - 1) : 0, live ? clampi(gx, 0, W - 1) : 0, chv ? c0 : 0, ok);
-        }
+        issue_halo<GK, NTH>(rawD[c], aD, cxg, n, ty0, tx0, H, W, tid, c0, c0 < aD.C, live);
       }
     }
 #pragma unroll
@@ -227,21 +181,17 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
       }
     }
     if (NA1 > 0) {
-      const int sy_base = hpfg_conv16::up_base(ty0, p.xa1.Hs), sx_base = hpfg_conv16::up_base(tx0, p.xa1.Ws);
-      const int pix = tid >> 1;
-      const int sy = live ? clampi(sy_base + pix / USW, 0, p.xa1.Hs - 1) : 0, sx = live ? clampi(sx_base + pix % USW, 0, p.xa1.Ws - 1) : 0;
+      const int sy_base = up_base(ty0, p.xa1.Hs), sx_base = up_base(tx0, p.xa1.Ws);      // (the interior tile: no halo)
 #pragma unroll
       for (int c = 0; c < NA1; ++c) {
         if ((NA0 + c < PFA) != EARLY) continue;
         const int cu = c * 16 + gsel * 8;                // channel inside the upsampled tensor
-        const int off = ((n * p.xa1.Hs + sy) * p.xa1.Ws + sx) * p.xa1.pstride + (cu < p.xa1.C ? cu : 0);
-        rawU[c][0] = ld4(p.xa1.z, off);
-        rawU[c][1] = ld4(p.xa1.z, off + 4);
+        up_patch_issue<UP::SW>(rawU[c], p.xa1, n, sy_base, sx_base, live ? tid >> 1 : 0, cu < p.xa1.C ? cu : 0);
       }
     }
   };
 
-  int w = xg * per_x + xj;
+  int w = tw.w;
   if (w < wend) issue(std::true_type{}, w / ntiles, ((w % ntiles) / tiles_x) * T, ((w % ntiles) % tiles_x) * T, true);
   __syncthreads();                                       // tables
   HPFG_TR(2)
@@ -254,33 +204,9 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
 #pragma unroll
     for (int c = 0; c < CO; ++c) {
       const int c0 = c * 16 + gsel * 8;
-      const bool chv = c0 < aD.C;
       Tab tg;
-      if (GK == HPFG_KIND_DZ) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          tg.sc[h] = ld4(tabD, 0 * 16 * CO + c0 + 4 * h);
-          tg.sh[h] = ld4(tabD, 1 * 16 * CO + c0 + 4 * h);
-          tg.k1[h] = ld4(tabD, 2 * 16 * CO + c0 + 4 * h);
-          tg.k2[h] = ld4(tabD, 3 * 16 * CO + c0 + 4 * h);
-          tg.k3[h] = ld4(tabD, 4 * 16 * CO + c0 + 4 * h);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < ND; ++i) {
-        const int idx = tid + i * NTH, pix = idx >> 1;
-        const int gy = ty0 + pix / HP - 1, gx = tx0 + pix % HP - 1;
-        const bool ok = idx < HP * HP * 2 && chv && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        f32x4 v0, v1;
-        finish_piece<GK>(v0, v1, rawD[c][i], tg, aD, none, cxg, n, clampi(gy, 0, H - 1), clampi(gx, 0, W - 1), chv ? c0 : 0, ok);
-        if (idx < HP * HP * 2) {
-          bf16x8 hi, lo;
-          split8(v0, v1, hi, lo);
-          unsigned char* o = ldsD + c * DCH + ((pix / HP) * RS + pix % HP) * 32 + gsel * 16;
-          *reinterpret_cast<bf16x8*>(o) = hi;
-          *reinterpret_cast<bf16x8*>(o + DPL) = lo;
-        }
-      }
+      load_tables_lds<GK, 16 * CO>(tg, tabD, aD, c0);
+      stage_halo<GK, NTH>(ldsD + c * DCH, rawD[c], tg, aD, cxg, n, ty0, tx0, H, W, tid, c0, c0 < aD.C);
     }
     // (prefetched chunks come first: the ones requested at the top of this iteration get the time of that conversion to arrive)
 #pragma unroll
@@ -288,11 +214,7 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
       const int c0 = c * 16 + gsel * 8;
       const bool chv = c0 < aS.C;
       Tab ta;
-#pragma unroll
-      for (int h = 0; h < 2 && AK0 != HPFG_KIND_PLAIN; ++h) {
-        ta.sc[h] = ld4(tabA, 0 * 16 * NA0 + c0 + 4 * h);
-        ta.sh[h] = ld4(tabA, 1 * 16 * NA0 + c0 + 4 * h);
-      }
+      load_tables_lds<AK0, 16 * NA0>(ta, tabA, aS, c0);
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int pix = (tid + i * NTH) >> 1;
@@ -310,19 +232,16 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
       }
     }
     if (NA1 > 0) {
-      if (tid < USH * USW * 2) {
+      if (tid < UP::SH * UP::SW * 2) {
 #pragma unroll
-        for (int c = 0; c < NA1; ++c) {
-          float* d = ldsU + c * (UBYTES / 4) + (tid >> 1) * 16 + gsel * 8;
-          *reinterpret_cast<f32x4*>(d) = rawU[c][0];
-          *reinterpret_cast<f32x4*>(d + 4) = rawU[c][1];
-        }
+        for (int c = 0; c < NA1; ++c) up_patch_park<16>(ldsU + c * (UBYTES / 4), rawU[c], tid >> 1, gsel * 8);
       }
       __syncthreads();
-      const int sy_base = hpfg_conv16::up_base(ty0, p.xa1.Hs), sx_base = hpfg_conv16::up_base(tx0, p.xa1.Ws);
+      const int sy_base = up_base(ty0, p.xa1.Hs), sx_base = up_base(tx0, p.xa1.Ws);
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int pix = (tid + i * NTH) >> 1;
+        // (the text of up_blend, not a call: stage.h says why)
         int y0, y1, x0, x1;
         float wy1, wx1;
         up_coord(ty0 + pix / T, p.xa1.Hs, y0, y1, wy1);
@@ -332,14 +251,14 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
 #pragma unroll
         for (int c = 0; c < NA1; ++c) {
           const bool chv = c * 16 + gsel * 8 < p.xa1.C;
-          const float* r0 = ldsU + c * (UBYTES / 4) + ((y0 - sy_base) * USW) * 16 + gsel * 8;
-          const float* r1 = ldsU + c * (UBYTES / 4) + ((y1 - sy_base) * USW) * 16 + gsel * 8;
+          const float* r0 = ldsU + c * (UBYTES / 4) + ((y0 - sy_base) * UP::SW) * 16 + gsel * 8;
+          const float* r1 = ldsU + c * (UBYTES / 4) + ((y1 - sy_base) * UP::SW) * 16 + gsel * 8;
           const f32x4 a00 = *reinterpret_cast<const f32x4*>(r0 + o0), b00 = *reinterpret_cast<const f32x4*>(r0 + o0 + 4);
           const f32x4 a01 = *reinterpret_cast<const f32x4*>(r0 + o1), b01 = *reinterpret_cast<const f32x4*>(r0 + o1 + 4);
           const f32x4 a10 = *reinterpret_cast<const f32x4*>(r1 + o0), b10 = *reinterpret_cast<const f32x4*>(r1 + o0 + 4);
           const f32x4 a11 = *reinterpret_cast<const f32x4*>(r1 + o1), b11 = *reinterpret_cast<const f32x4*>(r1 + o1 + 4);
-          f32x4 v0 = wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11);     // same expression order as finish_piece<CAT>
-          f32x4 v1 = wy0 * (wx0 * b00 + wx1 * b01) + wy1 * (wx0 * b10 + wx1 * b11);
+          f32x4 v0 = bilerp(wy0, wy1, wx0, wx1, a00, a01, a10, a11);
+          f32x4 v1 = bilerp(wy0, wy1, wx0, wx1, b00, b01, b10, b11);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             v0[j] = chv ? v0[j] : 0.f;
@@ -446,13 +365,13 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
 #pragma unroll
       for (int ks = 0; ks < T / 2; ++ks) {
         const unsigned char* ap = Ai + (2 * ks * T) * 32;
-        const bf16x8 ah = tr8(ap, ap + T * 32), al = tr8(ap + APL, ap + APL + T * 32);
+        const bf16x8 ah = tr_read8(ap, ap + T * 32), al = tr_read8(ap + APL, ap + APL + T * 32);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int tap = wt0 + t * TSTR < 9 ? wt0 + t * TSTR : 8;
           const int ky = tap / 3, kx = tap - 3 * ky;
           const unsigned char* dp = Dj + ((2 * ks - ky + 2) * RS + (2 - kx)) * 32;
-          const bf16x8 gh = tr8(dp, dp + RS * 32), gl_ = tr8(dp + DPL, dp + DPL + RS * 32);
+          const bf16x8 gh = tr_read8(dp, dp + RS * 32), gl_ = tr_read8(dp + DPL, dp + DPL + RS * 32);
           accw[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gh, accw[a][t], 0, 0, 0);
           accw[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gl_, accw[a][t], 0, 0, 0);
           accw[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, gh, accw[a][t], 0, 0, 0);

@@ -1,5 +1,25 @@
-// Staging helpers shared by the split-bf16 conv and wgrad kernels: per-kind raw loads of an 8-channel piece of a virtual
-// activation (issue_piece), the producer chain on the loaded values (finish_piece), and the bf16 hi/lo split.
+// Staging code shared by the four split-bf16 kernel families -- the chunked 3x3 / 1x1 kernels (conv_bf16_kernel.h), the whole-tile forward
+// kernel (conv_thin_kernel.h), the fused dgrad + wgrad kernel (fused_bwd_kernel.h) and the weight gradient (wgrad_bf16_kernel.h).  Each phase
+// below has ONE definition; the kernels differ in the template constants and arguments they pass, never by a branch in here:
+//   * per piece: raw loads of an 8-channel piece of a virtual activation (issue_piece), the producer chain (finish_piece), the bf16 hi / lo
+//     split (split8, split_piece) -- all four families;
+//   * per-channel source tables: LDS rows filled once per launch (fill_tables_lds; row stride and row length are the caller's) and read
+//     back into a Tab (load_tables_lds<KIND, STRIDE>) -- all four families;
+//   * the upsampled half of a concat source through an LDS patch: geometry (UpPatch), first source row / column (up_base), the patch
+//     piece of a thread (up_patch_issue), parking it (up_patch_park), the blend expression (bilerp: what finish_piece<CAT> computes) --
+//     all four families; the blend of an output piece's four taps from the patch (up_blend) -- chunked, weight gradient.  Patch channel
+//     stride and width are template constants, the halo and the validity mask are the caller's arguments;
+//   * the XCD-contiguous tile walk (tile_walk) -- all four families; the number of XCD groups is the caller's (see there);
+//   * the transposing LDS read of the kernels that contract over pixels (tr_read8) -- fused, weight gradient;
+//   * the in-kernel time stamps of the diagnostics build (HPFG_TR, HPFG_TR_REAL) -- chunked, fused, weight gradient.
+// The whole-tile layout that the thin and the fused kernel share on top of this is tile16.h.
+// Deliberate exceptions (a phase stays a family's own text where the shared form would need a branch on its caller, or changes a result):
+//   * thin and fused kernel, the blend of an output piece: the text of up_blend around the shared expression (bilerp), not a call.  Built
+//     from the call, the compiler contracts the blend's first row the other way round (wx1 * a01 fused, wx0 * a00 multiplied) in these two
+//     families: one ulp on the staged values, and the digests of tests/golden/conv_bits.json change for every concat case of the two;
+//   * weight gradient, tables of the layer input: load_tables (registers, straight from the table, once per workgroup: its 16 NI channels
+//     do not change with the work item), not the LDS rows;
+//   * weight gradient, SPLIT16 operands: their issue is an address select and their staging a copy (wgrad_bf16_kernel.h), no piece chain.
 #pragma once
 #include "common.h"
 
@@ -30,6 +50,51 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& h
 }
 
 __device__ __forceinline__ f32x4 ld4(const float* base, int off) { return *reinterpret_cast<const f32x4*>(base + off); }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }   // v_med3_i32
+
+// ds_read_b64_tr_b16 twice: row0 / row1 are this lane's addresses inside two 4-pixel blocks of a pixel-major [pixel][16 ch] bf16 image
+// (wgrad_bf16_kernel.h); the result is 8 k-values (pixels) of this lane's channel
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ bf16x8 tr_read8(const unsigned char* row0, const unsigned char* row1) {
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(row0));
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(row1));
+  return __builtin_bit_cast(bf16x8, (s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}));
+}
+
+// Diagnostics build only (make TRACE=1 -> libhpfg_hip_trace.so, tools/trace_conv.py, tools/trace_fused.py): with math bit 0x2000 one thread
+// of every workgroup writes (id << 56 | s_memtime) stamps to the kernel's own u64 buffer tr_buf (256 per workgroup; the kernel says where).
+#ifdef HPFG_TRACE
+#define HPFG_TR(ID)                                                                                        \
+  if (tr_on && tr_i < 255) {                                                                               \
+    tr_buf[tr_i++] = ((unsigned long long)(ID) << 56) | (__builtin_amdgcn_s_memtime() & 0xffffffffffffffull); \
+  }
+#define HPFG_TR_REAL(ID)                                                                                   \
+  if (tr_on && tr_i < 255) {                                                                               \
+    tr_buf[tr_i++] = ((unsigned long long)(ID) << 56) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffffffffull); \
+  }
+#else
+#define HPFG_TR(ID)
+#define HPFG_TR_REAL(ID)
+#endif
+
+// XCD-aware work mapping of the persistent kernels: workgroups are dealt round-robin over the 8 XCDs (b % 8 names the XCD group), each XCD
+// has its own L2.  Give every XCD group a CONTIGUOUS range of tiles (row-major inside an image) so that tiles sharing a halo are read
+// through the same L2; inside a group, workgroup j takes tiles j, j + step, j + 2 step, ... of the range.  (Speed only: any mapping is
+// correct.)  nx = 8 where blockIdx.x % 8 names the XCD, else 1 -- the caller's to say: a 1-D or (x, slice) grid with at least 8 workgroups
+// in x, or the weight gradient's (x, ci, co) grid, whose linear workgroup id is x + gridDim.x * (...) and needs gridDim.x % 8 == 0.
+struct TileWalk {
+  int w, wend, step;      // first work item of this workgroup, end of its group's range, workgroups of the group = stride
+};
+__device__ __forceinline__ TileWalk tile_walk(int nwork, int nx) {
+  const int xg = (int)blockIdx.x % nx, xj = (int)blockIdx.x / nx;
+  const int per_x = (nwork + nx - 1) / nx;                 // tiles per XCD group
+  TileWalk t;
+  t.wend = (xg + 1) * per_x < nwork ? (xg + 1) * per_x : nwork;
+  t.step = ((int)gridDim.x - xg + nx - 1) / nx;
+  t.w = xg * per_x + xj;
+  return t;
+}
 
 // ---- per-kind staging: issue_piece() puts the raw global loads of one 8-channel piece in flight, finish_piece() applies the
 // ---- producer chain.  Raw loads per piece: PLAIN/BNACT 2, DZ 4 (z + dA), POOL 8 (2x2 pixels), CAT 8 (4 bilinear taps).
@@ -69,34 +134,36 @@ __device__ __forceinline__ void load_tables(Tab& t, const HpfgAct& a0, int c0, b
   }
 }
 
-// The forward kinds (BNACT / POOL / concat skip half) read scale / shift of the whole source from LDS rows the kernel prologue filled
-// (hpfg_bn_rows_to_lds: from the table, or derived from the producer's sum accumulators).
+// The kinds with a producer chain (BNACT / POOL / concat skip half: scale, shift; DZ: scale, shift, k1, k2, k3) read the rows of the whole
+// source from LDS rows [row][STRIDE] the kernel prologue filled (from the table, or derived from the sum accumulators: common.h).  STRIDE is
+// HPFG_BN_CMAX in the chunked kernels, which serve any source, and the channel count of the instantiation in the others.
 constexpr int HPFG_BN_CMAX = 256;      // channels of a BatchNorm'd source whose coefficients a consumer keeps in LDS
 template <int KIND>
 constexpr bool tab_in_lds() { return KIND == HPFG_KIND_BNACT || KIND == HPFG_KIND_POOL || KIND == HPFG_KIND_CAT || KIND == HPFG_KIND_DZ; }
 template <int KIND>
 constexpr int tab_rows() { return KIND == HPFG_KIND_DZ ? 5 : 2; }      // scale, shift [, k1, k2, k3]
-template <int KIND>
+template <int KIND, int STRIDE = HPFG_BN_CMAX>
 __device__ __forceinline__ void load_tables_lds(Tab& t, const float* ldsT, const HpfgAct& a0, int c0) {
-  if (KIND == HPFG_KIND_CAT && c0 >= a0.C) return;
+  if (!tab_in_lds<KIND>() || (KIND == HPFG_KIND_CAT && c0 >= a0.C)) return;
   t.sc[0] = ld4(ldsT, c0);
   t.sc[1] = ld4(ldsT, c0 + 4);
-  t.sh[0] = ld4(ldsT, HPFG_BN_CMAX + c0);
-  t.sh[1] = ld4(ldsT, HPFG_BN_CMAX + c0 + 4);
+  t.sh[0] = ld4(ldsT, STRIDE + c0);
+  t.sh[1] = ld4(ldsT, STRIDE + c0 + 4);
   if (KIND == HPFG_KIND_DZ) {
-    t.k1[0] = ld4(ldsT, 2 * HPFG_BN_CMAX + c0);
-    t.k1[1] = ld4(ldsT, 2 * HPFG_BN_CMAX + c0 + 4);
-    t.k2[0] = ld4(ldsT, 3 * HPFG_BN_CMAX + c0);
-    t.k2[1] = ld4(ldsT, 3 * HPFG_BN_CMAX + c0 + 4);
-    t.k3[0] = ld4(ldsT, 4 * HPFG_BN_CMAX + c0);
-    t.k3[1] = ld4(ldsT, 4 * HPFG_BN_CMAX + c0 + 4);
+    t.k1[0] = ld4(ldsT, 2 * STRIDE + c0);
+    t.k1[1] = ld4(ldsT, 2 * STRIDE + c0 + 4);
+    t.k2[0] = ld4(ldsT, 3 * STRIDE + c0);
+    t.k2[1] = ld4(ldsT, 3 * STRIDE + c0 + 4);
+    t.k3[0] = ld4(ldsT, 4 * STRIDE + c0);
+    t.k3[1] = ld4(ldsT, 4 * STRIDE + c0 + 4);
   }
 }
-// the kernel prologue's fill of those rows
-template <int KIND>
-__device__ __forceinline__ void fill_tables_lds(const HpfgAct& a0, float* ldsT, int tid, int nthr) {
-  if (KIND == HPFG_KIND_DZ) hpfg_dz_rows_to_lds(a0, ldsT, HPFG_BN_CMAX, a0.C, tid, nthr);
-  else hpfg_bn_rows_to_lds(a0, ldsT, HPFG_BN_CMAX, tid, nthr);
+// the kernel prologue's fill of those rows: channels [0, nch) of every row, zeros at and past a0.C (all threads call, the caller syncs).
+// ACC = false: scale / shift from the table rows even where a0.bn_acc is set (common.h)
+template <int KIND, int STRIDE = HPFG_BN_CMAX, bool ACC = true>
+__device__ __forceinline__ void fill_tables_lds(const HpfgAct& a0, float* ldsT, int nch, int tid, int nthr) {
+  if (KIND == HPFG_KIND_DZ) hpfg_dz_rows_to_lds(a0, ldsT, STRIDE, nch, tid, nthr);
+  else if (tab_in_lds<KIND>()) hpfg_bn_rows_to_lds<ACC>(a0, ldsT, STRIDE, nch, tid, nthr);
 }
 
 // bilinear x2 (align_corners=True) source taps of output coordinate o for a low-res extent L
@@ -106,6 +173,68 @@ __device__ __forceinline__ void up_coord(int o, int L, int& i0, int& i1, float& 
   i0 = (int)f;
   i1 = i0 + (i0 < L - 1 ? 1 : 0);
   w1 = f - (float)i0;
+}
+
+// the blend of the four taps (a00 a01 / a10 a11) of one output value: THE expression of the upsampled half, on float4 values; the compiler is
+// free to contract it into FMAs
+__device__ __forceinline__ f32x4 bilerp(float wy0, float wy1, float wx0, float wx1, const f32x4& a00, const f32x4& a01, const f32x4& a10,
+                                        const f32x4& a11) {
+  return wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11);
+}
+
+// ---- Concat loader, upsampled half through an LDS patch: the bilinear x2 taps of a TH x TW tile (with or without a halo pixel) come from a
+// (TH/2+3) x (TW/2+3) patch of the low-resolution 1x1-conv output.  That patch is fetched ONCE per tile and chunk of CW channels (a thread
+// requests one 8-channel piece, two float4, prefetched like the cheap loaders), parked in LDS as fp32 [pixel][CW channels], and every output
+// piece interpolates its four taps from LDS -- instead of 8 float4 global loads per output piece (24 per thread and chunk in the chunked
+// kernel), whose registers forced a two-k-step pipeline that exposed one memory latency per piece.
+template <int TH, int TW>
+struct UpPatch {
+  static constexpr int SH = TH / 2 + 3, SW = TW / 2 + 3;
+};
+// first low-res row / column a tile touches: source index of output coordinate max(o0, 0) (o0 = the tile's first row / column, halo included)
+__device__ __forceinline__ int up_base(int o0, int L) {
+  const float r = L > 1 ? (float)(L - 1) / (float)(2 * L - 1) : 0.f;
+  return (int)(r * (float)(o0 < 0 ? 0 : o0));
+}
+// this thread's piece of the patch of image n at (sy_base, sx_base): patch pixel `pix`, channels cu .. cu + 7 of the upsampled tensor
+template <int SW>
+__device__ __forceinline__ void up_patch_issue(f32x4 (&rawU)[2], const HpfgAct& u, int n, int sy_base, int sx_base, int pix, int cu) {
+  const int sy = clampi(sy_base + pix / SW, 0, u.Hs - 1), sx = clampi(sx_base + pix % SW, 0, u.Ws - 1);
+  const int off = ((n * u.Hs + sy) * u.Ws + sx) * u.pstride + cu;
+  rawU[0] = ld4(u.z, off);
+  rawU[1] = ld4(u.z, off + 4);
+}
+template <int CW>
+__device__ __forceinline__ void up_patch_park(float* ldsU, const f32x4 (&rawU)[2], int pix, int cg) {
+  float* d = ldsU + pix * CW + cg;
+  *reinterpret_cast<f32x4*>(d) = rawU[0];
+  *reinterpret_cast<f32x4*>(d + 4) = rawU[1];
+}
+// (v0, v1) = channels cg .. cg + 7 of output pixel (gy, gx) (clamped into the image by the caller) from the parked patch; zeros unless ok.
+// The expression tree is finish_piece<CAT>'s -- the kernels agree to the bit with the per-piece loader (tests/test_gpu_conv_thin.py, the
+// float64 bound of tests/helpers.py states it with the u * f term) up to how one compilation contracts it into FMAs.
+template <int CW, int SW>
+__device__ __forceinline__ void up_blend(f32x4& v0, f32x4& v1, const float* ldsU, const HpfgAct& u, int gy, int gx, int sy_base, int sx_base,
+                                         int cg, bool ok) {
+  int y0, y1, x0, x1;
+  float wy1, wx1;
+  up_coord(gy, u.Hs, y0, y1, wy1);
+  up_coord(gx, u.Ws, x0, x1, wx1);
+  const float wy0 = 1.f - wy1, wx0 = 1.f - wx1;
+  const float* r0 = ldsU + ((y0 - sy_base) * SW) * CW + cg;
+  const float* r1 = ldsU + ((y1 - sy_base) * SW) * CW + cg;
+  const int o0 = (x0 - sx_base) * CW, o1 = (x1 - sx_base) * CW;
+  const f32x4 a00 = *reinterpret_cast<const f32x4*>(r0 + o0), b00 = *reinterpret_cast<const f32x4*>(r0 + o0 + 4);
+  const f32x4 a01 = *reinterpret_cast<const f32x4*>(r0 + o1), b01 = *reinterpret_cast<const f32x4*>(r0 + o1 + 4);
+  const f32x4 a10 = *reinterpret_cast<const f32x4*>(r1 + o0), b10 = *reinterpret_cast<const f32x4*>(r1 + o0 + 4);
+  const f32x4 a11 = *reinterpret_cast<const f32x4*>(r1 + o1), b11 = *reinterpret_cast<const f32x4*>(r1 + o1 + 4);
+  v0 = bilerp(wy0, wy1, wx0, wx1, a00, a01, a10, a11);
+  v1 = bilerp(wy0, wy1, wx0, wx1, b00, b01, b10, b11);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v0[j] = ok ? v0[j] : 0.f;
+    v1[j] = ok ? v1[j] : 0.f;
+  }
 }
 
 template <int KIND>
@@ -233,8 +362,8 @@ __device__ __forceinline__ void finish_piece(f32x4& v0, f32x4& v1, const RawPiec
     up_coord(gy, u.Hs, i0, i1, wy1);
     up_coord(gx, u.Ws, i0, i1, wx1);
     const float wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-    v0 = wy0 * (wx0 * raw[0] + wx1 * raw[2]) + wy1 * (wx0 * raw[4] + wx1 * raw[6]);
-    v1 = wy0 * (wx0 * raw[1] + wx1 * raw[3]) + wy1 * (wx0 * raw[5] + wx1 * raw[7]);
+    v0 = bilerp(wy0, wy1, wx0, wx1, raw[0], raw[2], raw[4], raw[6]);
+    v1 = bilerp(wy0, wy1, wx0, wx1, raw[1], raw[3], raw[5], raw[7]);
   } else {   // DZ: k1*g + k2*z + k3, g = dA * dropmask/(1-p) * lrelu'(scale*z+shift)
     f32x4 ga = raw[2], gb = raw[3];
     if (a.drop_p > 0.f) {

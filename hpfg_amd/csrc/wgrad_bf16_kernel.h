@@ -24,7 +24,6 @@
 namespace hpfg_wg16 {
 
 using namespace hpfg_stage;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TH = 8, TW = 16;
 constexpr int G_PLANE = TH * TW * 32;          // bytes per hi / lo plane of one output-channel tile
@@ -38,49 +37,20 @@ struct Geo {                                   // A tile: 3x3 with a 1-pixel hal
   static constexpr int A_PLANE = A_SLOTS * 32; // bytes per hi / lo plane of one input-channel tile
 };
 
-// concat A source: the upsampled half's bilinear taps of an (8+2)x(16+2) tile come from a 7x11 low-res patch (see conv_bf16_kernel.h)
-constexpr int UP_SH = TH / 2 + 3, UP_SW = TW / 2 + 3;
+// concat A source: the upsampled half's bilinear taps of an (8+2)x(16+2) tile come from a 7x11 low-res patch (stage.h)
+using UP = UpPatch<TH, TW>;
 
 template <int NI, int NJ, int TAPS>
 struct Lds {
   static constexpr int A_BYTES = NI * 2 * Geo<TAPS>::A_PLANE;
   static constexpr int G_BYTES = NJ * 2 * G_PLANE;
-  static constexpr int UP_BYTES = UP_SH * UP_SW * 16 * NI * 4;      // fp32 patch [pixel][16 NI channels] (concat sources only)
+  static constexpr int UP_BYTES = UP::SH * UP::SW * 16 * NI * 4;      // fp32 patch [pixel][16 NI channels] (concat sources only)
   static constexpr int BYTES = A_BYTES + G_BYTES;
 };
 
 // a 32-byte zero piece: an out-of-image (or padding) piece of a SPLIT16 source is LOADED from here -- one 64-bit address select instead of
 // eight value selects per piece, and no clamped coordinates to compute
 static __device__ __attribute__((aligned(32))) const float hpfg_zero_piece[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-__device__ __forceinline__ bf16x8 tr_read8(const unsigned char* row0, const unsigned char* row1) {
-  // row0/row1: this lane's addresses inside the two 4-pixel blocks (see header); result = 8 k-values of this lane's channel
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(row0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(row1));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// diagnostics build (make TRACE=1): math bit 0x2000 -> thread 0 of every workgroup stamps s_memtime into slab + 256 * block (u64)
-#ifdef HPFG_TRACE
-#define HPFG_WTR(ID)                                                                                        \
-  if (tr_on && tr_i < 255) {                                                                                \
-    tr_buf[tr_i++] = ((unsigned long long)(ID) << 56) | (__builtin_amdgcn_s_memtime() & 0xffffffffffffffull); \
-  }
-#define HPFG_WTR_REAL(ID)                                                                                   \
-  if (tr_on && tr_i < 255) {                                                                                \
-    tr_buf[tr_i++] = ((unsigned long long)(ID) << 56) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffffffffull); \
-  }
-#else
-#define HPFG_WTR(ID)
-#define HPFG_WTR_REAL(ID)
-#endif
-
-__device__ __forceinline__ int up_base_w(int o0, int L) {      // first low-res row / column a tile with halo touches
-  const float r = L > 1 ? (float)(L - 1) / (float)(2 * L - 1) : 0.f;
-  return (int)(r * (float)(o0 < 0 ? 0 : o0));
-}
 
 // One staging piece of a thread: tile-invariant local pixel and LDS byte offset (ly < 0 marks a padding piece beyond the tile).
 struct WPiece {
@@ -113,14 +83,14 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
   const int H = p.H, W = p.W;
   const ActCtx cxa = make_ctx(p.a0), cxg = make_ctx(p.g);
   const HpfgAct none = {};
-#ifdef HPFG_TRACE
+#ifdef HPFG_TRACE      // diagnostics build (make TRACE=1): thread 0 of every workgroup stamps into slab + 256 * block (u64)
   const bool tr_on = (p.math & 0x2000) && tid == 0;
   unsigned long long* tr_buf =
       reinterpret_cast<unsigned long long*>(p.slab) + 256 * (((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
   int tr_i = 0;
 #endif
-  HPFG_WTR_REAL(11)
-  HPFG_WTR(1)
+  HPFG_TR_REAL(11)
+  HPFG_TR(1)
 
   constexpr int TSTR = 4 / (NI * NJ);               // tap stride between the taps of one wave
   constexpr int NT = (TAPS + TSTR - 1) / TSTR;      // taps per wave (padded)
@@ -143,7 +113,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
     HpfgAct gs = p.g;          // this workgroup's 16 NJ output channels
     gs.bn_coff += co0;
     gs.C = p.g.C - co0 < 16 * NJ ? p.g.C - co0 : 16 * NJ;
-    hpfg_dz_rows_to_lds(gs, &ldsTG[0][0], 16 * NJ, 16 * NJ, tid, NTHR);
+    fill_tables_lds<HPFG_KIND_DZ, 16 * NJ>(gs, &ldsTG[0][0], 16 * NJ, tid, NTHR);
   }
 
   // Staging is batched: every global load of a batch is in flight before the first one is consumed (a thread owns NA pieces of
@@ -151,7 +121,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
   // pieces + the first GB dZ pieces, and batch 0 of the NEXT work item is requested before the MFMA phase of the current one.
   constexpr int NRA = RawCount<SA>::N, NRG = RawCount<GK>::N;
   constexpr int CW = 16 * NI;                               // channels of the patch
-  constexpr int NU = CATA ? (UP_SH * UP_SW * GA + NTHR - 1) / NTHR : 1;   // patch pieces per thread
+  constexpr int NU = CATA ? (UP::SH * UP::SW * GA + NTHR - 1) / NTHR : 1;   // patch pieces per thread
   constexpr int NA = (A_SLOTS * GA + NTHR - 1) / NTHR;
   constexpr int NG = (TH * TW * GG + NTHR - 1) / NTHR;
   constexpr int GB = NG < 2 ? NG : 2;                       // dZ pieces per batch
@@ -196,16 +166,9 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
   f32x4 rawU[NU][2];
 #define HPFG_WG_U_ISSUE()                                                                              \
   {                                                                                                   \
-    const int sy_b = up_base_w(ty0 - 1, p.a1.Hs), sx_b = up_base_w(tx0 - 1, p.a1.Ws);                 \
-    _Pragma("unroll") for (int i = 0; i < NU; ++i) {                                                  \
-      const int pix = (tid + i * NTHR) / GA;                                                          \
-      int sy = sy_b + pix / UP_SW, sx = sx_b + pix % UP_SW;                                           \
-      sy = sy > p.a1.Hs - 1 ? p.a1.Hs - 1 : sy;                                                       \
-      sx = sx > p.a1.Ws - 1 ? p.a1.Ws - 1 : sx;                                                       \
-      const int off = ((n * p.a1.Hs + sy) * p.a1.Ws + sx) * p.a1.pstride + (cva ? ca - p.a0.C : 0);   \
-      rawU[i][0] = ld4(p.a1.z, off);                                                                  \
-      rawU[i][1] = ld4(p.a1.z, off + 4);                                                              \
-    }                                                                                                 \
+    const int sy_b = up_base(ty0 - 1, p.a1.Hs), sx_b = up_base(tx0 - 1, p.a1.Ws);                     \
+    _Pragma("unroll") for (int i = 0; i < NU; ++i)                                                    \
+      up_patch_issue<UP::SW>(rawU[i], p.a1, n, sy_b, sx_b, (tid + i * NTHR) / GA, cva ? ca - p.a0.C : 0); \
   }
 
 #define HPFG_WG_A_COORD(I)                                                                            \
@@ -247,13 +210,11 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
   const int ntiles = tiles_x * tiles_y;
   const int nwork = p.N * ntiles;
 
-  // XCD-aware work mapping: workgroups are dealt round-robin over the 8 XCDs (the linear workgroup id is x + S * (...), S % 8 == 0, so
-  // x % 8 names the XCD and every (ci, co) pair of one pixel range already shares an L2).  Give every XCD a CONTIGUOUS range of pixel tiles,
-  // swept side by side by its workgroups, so that tiles sharing a halo meet in one L2 as well.
-  const int nxcd = gridDim.x % 8 == 0 ? 8 : 1;
-  const int per_x = (nwork + nxcd - 1) / nxcd, wstep = (int)gridDim.x / nxcd;
-  const int wend = ((int)blockIdx.x % nxcd + 1) * per_x < nwork ? ((int)blockIdx.x % nxcd + 1) * per_x : nwork;
-  int wk = ((int)blockIdx.x % nxcd) * per_x + (int)blockIdx.x / nxcd;
+  // XCD-aware work mapping (tile_walk): the linear workgroup id is x + S * (...), so with S % 8 == 0 x % 8 names the XCD and every (ci, co)
+  // pair of one pixel range already shares an L2; the contiguous ranges make tiles that share a halo meet in one L2 as well.
+  const TileWalk tw = tile_walk(nwork, gridDim.x % 8 == 0 ? 8 : 1);
+  const int wend = tw.wend, wstep = tw.step;
+  int wk = tw.w;
   if (wk < wend) {
     const int n = wk / ntiles, tile = wk % ntiles;
     const int ty0 = (tile / tiles_x) * TH, tx0 = (tile % tiles_x) * TW;
@@ -270,47 +231,26 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
       HPFG_WG_G_ISSUE(i, rawG[i])
     }
   }
-  HPFG_WTR(2)
+  HPFG_TR(2)
   for (; wk < wend; wk += wstep) {
     const int n = wk / ntiles, tile = wk % ntiles;
     const int ty0 = (tile / tiles_x) * TH, tx0 = (tile % tiles_x) * TW;
     __syncthreads();            // the previous item's MFMA phase has finished reading the tiles
-    HPFG_WTR(3)
+    HPFG_TR(3)
     if (a_up) {
-      // park the low-res patch, then blend every A piece's four taps from LDS (same expression order as finish_piece<CAT>)
-      const int sy_b = up_base_w(ty0 - 1, p.a1.Hs), sx_b = up_base_w(tx0 - 1, p.a1.Ws);
+      // park the low-res patch, then blend every A piece's four taps from LDS
+      const int sy_b = up_base(ty0 - 1, p.a1.Hs), sx_b = up_base(tx0 - 1, p.a1.Ws);
 #pragma unroll
       for (int i = 0; i < NU; ++i) {
         const int idx = tid + i * NTHR;
-        if (idx < UP_SH * UP_SW * GA) {
-          float* d = ldsU + (idx / GA) * CW + ga;
-          *reinterpret_cast<f32x4*>(d) = rawU[i][0];
-          *reinterpret_cast<f32x4*>(d + 4) = rawU[i][1];
-        }
+        if (idx < UP::SH * UP::SW * GA) up_patch_park<CW>(ldsU, rawU[i], idx / GA, ga);
       }
       __syncthreads();
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         HPFG_WG_A_COORD(i)
-        int y0, y1, x0, x1;
-        float wy1, wx1;
-        up_coord(gyc, p.a1.Hs, y0, y1, wy1);
-        up_coord(gxc, p.a1.Ws, x0, x1, wx1);
-        const float wy0 = 1.f - wy1, wx0 = 1.f - wx1;
-        const float* r0 = ldsU + ((y0 - sy_b) * UP_SW) * CW + ga;
-        const float* r1 = ldsU + ((y1 - sy_b) * UP_SW) * CW + ga;
-        const int o0 = (x0 - sx_b) * CW, o1 = (x1 - sx_b) * CW;
-        const f32x4 a00 = *reinterpret_cast<const f32x4*>(r0 + o0), b00 = *reinterpret_cast<const f32x4*>(r0 + o0 + 4);
-        const f32x4 a01 = *reinterpret_cast<const f32x4*>(r0 + o1), b01 = *reinterpret_cast<const f32x4*>(r0 + o1 + 4);
-        const f32x4 a10 = *reinterpret_cast<const f32x4*>(r1 + o0), b10 = *reinterpret_cast<const f32x4*>(r1 + o0 + 4);
-        const f32x4 a11 = *reinterpret_cast<const f32x4*>(r1 + o1), b11 = *reinterpret_cast<const f32x4*>(r1 + o1 + 4);
-        f32x4 v0 = wy0 * (wx0 * a00 + wx1 * a01) + wy1 * (wx0 * a10 + wx1 * a11);
-        f32x4 v1 = wy0 * (wx0 * b00 + wx1 * b01) + wy1 * (wx0 * b10 + wx1 * b11);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v0[j] = ok ? v0[j] : 0.f;
-          v1[j] = ok ? v1[j] : 0.f;
-        }
+        f32x4 v0, v1;
+        up_blend<CW, UP::SW>(v0, v1, ldsU, p.a1, gyc, gxc, sy_b, sx_b, ga, ok);
         if (pa[i].real) {
           bf16x8 hi, lo;
           split8(v0, v1, hi, lo);
@@ -340,19 +280,8 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
         }
       }
     }
-    HPFG_WTR(4)
-    if (GK == HPFG_KIND_DZ) {
-      tg.sc[0] = *reinterpret_cast<const f32x4*>(&ldsTG[0][gg]);
-      tg.sc[1] = *reinterpret_cast<const f32x4*>(&ldsTG[0][gg + 4]);
-      tg.sh[0] = *reinterpret_cast<const f32x4*>(&ldsTG[1][gg]);
-      tg.sh[1] = *reinterpret_cast<const f32x4*>(&ldsTG[1][gg + 4]);
-      tg.k1[0] = *reinterpret_cast<const f32x4*>(&ldsTG[2][gg]);
-      tg.k1[1] = *reinterpret_cast<const f32x4*>(&ldsTG[2][gg + 4]);
-      tg.k2[0] = *reinterpret_cast<const f32x4*>(&ldsTG[3][gg]);
-      tg.k2[1] = *reinterpret_cast<const f32x4*>(&ldsTG[3][gg + 4]);
-      tg.k3[0] = *reinterpret_cast<const f32x4*>(&ldsTG[4][gg]);
-      tg.k3[1] = *reinterpret_cast<const f32x4*>(&ldsTG[4][gg + 4]);
-    }
+    HPFG_TR(4)
+    if (GK == HPFG_KIND_DZ) load_tables_lds<HPFG_KIND_DZ, 16 * NJ>(tg, &ldsTG[0][0], p.g, gg);
 #pragma unroll
     for (int b = 0; b < NGB; ++b) {
       if (b > 0) {
@@ -385,7 +314,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
         }
       }
     }
-    HPFG_WTR(5)
+    HPFG_TR(5)
     {   // batch 0 of the next work item goes out before the MFMA phase (clamped to the last item: harmless reload, no branch)
       const int wk2 = wk + wstep < wend ? wk + wstep : wk;
       const int n = wk2 / ntiles, tile = wk2 % ntiles;
@@ -403,9 +332,9 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
         HPFG_WG_G_ISSUE(i, rawG[i])
       }
     }
-    HPFG_WTR(6)
+    HPFG_TR(6)
     __syncthreads();
-    HPFG_WTR(7)
+    HPFG_TR(7)
     // ---- 4 MFMA k-steps of 32 pixels (2 tile rows each)
     if constexpr (NT == 9 && TAPS == 9) {
       // A wave that owns all nine taps (the 2 x 2 channel-rich shape): the A fragment of (k-step ks, kernel row ky) covers tile rows
@@ -466,7 +395,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
         }
       }
     }
-    HPFG_WTR(8)
+    HPFG_TR(8)
   }
 #undef HPFG_WG_A_ISSUE
 #undef HPFG_WG_G_ISSUE
@@ -476,8 +405,8 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
   // slab[s][tap][ci][co]; C/D layout: row (ci) = (lane>>4)*4 + r, col (co) = lane & 15
 #ifdef HPFG_TRACE
   if (p.math & 0x2000) {
-    HPFG_WTR(9)
-    HPFG_WTR_REAL(12)
+    HPFG_TR(9)
+    HPFG_TR_REAL(12)
     return;
   }
 #endif
