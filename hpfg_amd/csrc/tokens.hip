@@ -605,29 +605,66 @@ __global__ __launch_bounds__(256) void resize_bwd_kernel(const float* __restrict
 }
 
 // ---- BatchNorm (train) + ReLU + channel dropout over tokens [R, C] (ConvModule + Dropout2d of the head, segformer.py:288-296,307,318) ----
-// thread t <-> channel quad t % Q and row lane t / Q; part[blockIdx][2][C] partial sums, reduced in a fixed order by col_reduce_kernel
+// thread t <-> channel quad t % Q and row lane t / Q.  E[x^2] - mean^2 in fp32 loses the variance once |mean| >> std (a head feature with
+// mean 32 and std 1 keeps three digits), so nothing here squares x itself: every value is taken relative to the channel's pivot x[0][c]
+// (an exact fp32 subtraction for values of one magnitude), a workgroup sums z = x - pivot over its rows, and squares around ITS OWN mean.
+// part[blockIdx][0][C] = sum z, part[blockIdx][1][C] = sum (z - workgroup mean)^2; col_stats_finish_kernel combines them in double.
 __global__ __launch_bounds__(256) void col_stats_kernel(const float* __restrict__ x, long R, int C, float* __restrict__ part, int rows_per_wg) {
   __shared__ float red[256 * 8];
   const int Q = C >> 2, q = threadIdx.x % Q, pl = threadIdx.x / Q, PL = 256 / Q, c = q * 4;
+  const f32x4 piv = *reinterpret_cast<const f32x4*>(x + c);
   f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
   const long r0 = (long)blockIdx.x * rows_per_wg;
+  const long r1 = r0 + rows_per_wg < R ? r0 + rows_per_wg : R;          // (r1 <= r0: this workgroup owns no rows and writes zeros)
   if (pl < PL)
-    for (long r = r0 + pl; r < r0 + rows_per_wg && r < R; r += PL) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(x + r * C + c);
-      a += v;
-      b += v * v;
-    }
+    for (long r = r0 + pl; r < r1; r += PL) a += *reinterpret_cast<const f32x4*>(x + r * C + c) - piv;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    red[threadIdx.x * 8 + j] = a[j];
-    red[threadIdx.x * 8 + 4 + j] = b[j];
+  for (int j = 0; j < 4; ++j) red[threadIdx.x * 8 + j] = a[j];
+  __syncthreads();
+  if (pl < PL && r0 + pl < r1) {
+    f32x4 bm = {0.f, 0.f, 0.f, 0.f};          // the workgroup's mean of z: every row lane of a quad adds the same values in the same order
+    for (int l = 0; l < PL; ++l)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) bm[j] += red[(l * Q + q) * 8 + j];
+    bm = bm * (1.f / (float)(r1 - r0)) + piv;
+    for (long r = r0 + pl; r < r1; r += PL) {          // second read of the workgroup's own rows: L2 hits
+      const f32x4 d = *reinterpret_cast<const f32x4*>(x + r * C + c) - bm;
+      b += d * d;
+    }
   }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) red[threadIdx.x * 8 + 4 + j] = b[j];
   __syncthreads();
   for (int o = threadIdx.x; o < 2 * C; o += 256) {
     const int which = o / C, cc = o % C, qq = cc >> 2, j = cc & 3;
     float acc = 0.f;
     for (int l = 0; l < PL; ++l) acc += red[(l * Q + qq) * 8 + which * 4 + j];
     part[((long)blockIdx.x * 2 + which) * C + cc] = acc;
+  }
+}
+
+// sums[0][c] = sum_r x, sums[1][c] = sum_r (x - mean)^2 from the per-workgroup (sum z, centred squares) of col_stats_kernel: the squares of
+// workgroup b, which owns n_b rows, are around its own mean m_b, so the total is sum_b (M2_b + n_b (m_b - mean)^2) -- in double, fixed order
+__global__ __launch_bounds__(64) void col_stats_finish_kernel(const float* __restrict__ part, int nblk, int C, long R, int rows_per_wg,
+                                                              const float* __restrict__ x, float* __restrict__ sums) {
+  const int c = blockIdx.x;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 64) s += (double)part[((long)i * 2) * C + c];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+  const double mz = s / (double)R;
+  double m2 = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 64) {
+    const long r0 = (long)i * rows_per_wg, r1 = r0 + rows_per_wg < R ? r0 + rows_per_wg : R;
+    if (r1 <= r0) continue;
+    const double n = (double)(r1 - r0), d = (double)part[((long)i * 2) * C + c] / n - mz;
+    m2 += (double)part[((long)i * 2 + 1) * C + c] + n * d * d;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m2 += __shfl_xor(m2, o);
+  if (threadIdx.x == 0) {
+    sums[c] = (float)(s + (double)R * (double)x[c]);
+    sums[C + c] = (float)m2;
   }
 }
 
@@ -1025,18 +1062,19 @@ extern "C" int hpfg_tok_stat_blocks(long R) {
 
 static int tok_c_ok(int C) { return C % 4 == 0 && C >= 4 && C <= 1024 && 256 % (C / 4) == 0; }
 
-/* sums[0][C] = sum_r x, sums[1][C] = sum_r x^2 */
+/* sums[0][C] = sum_r x, sums[1][C] = sum_r (x - mean)^2: the biased batch variance is sums[1] / R, with nothing left to cancel */
 extern "C" int hpfg_tok_col_stats(const float* x, long R, int C, float* partials, float* sums, void* stream) {
   HPFG_ARG_CHECK(x && partials && sums && R > 0 && tok_c_ok(C), "tok_col_stats: bad args (C/4 must divide 256)");
   const int nblk = hpfg_tok_stat_blocks(R);
-  hipLaunchKernelGGL(col_stats_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, R, C, partials, (int)((R + nblk - 1) / nblk));
-  hipLaunchKernelGGL(col_reduce_kernel, dim3(2 * C), dim3(64), 0, (hipStream_t)stream, partials, nblk, 2 * C, sums);
+  const int per = (int)((R + nblk - 1) / nblk);
+  hipLaunchKernelGGL(col_stats_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, R, C, partials, per);
+  hipLaunchKernelGGL(col_stats_finish_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, partials, nblk, C, R, per, x, sums);
   return hpfg_launch_status("col_stats_kernel");
 }
 
 extern "C" int hpfg_bnrelu_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* mask,
                                  float inv_keep, long rows_per_image, float* y, long R, int C, void* stream) {
-  HPFG_ARG_CHECK(x && mean && rstd && gamma && beta && y && R > 0 && C % 4 == 0 && rows_per_image > 0, "bnrelu_apply: bad args");
+  HPFG_ARG_CHECK(x && mean && rstd && gamma && beta && y && R > 0 && C % 4 == 0 && C >= 4 && rows_per_image > 0, "bnrelu_apply: bad args");
   hipLaunchKernelGGL(bnrelu_apply_kernel, dim3(grid_cap(R * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, mask,
                      inv_keep, rows_per_image, y, R, C);
   return hpfg_launch_status("bnrelu_apply_kernel");

@@ -419,7 +419,7 @@ class _BNReLUDrop(torch.autograd.Function):
         sums = torch.empty(2, C_, dtype=torch.float32, device=x.device)
         L.check(lib.hpfg_tok_col_stats(L.ptr(xc), R, C_, L.ptr(part), L.ptr(sums), _st(x)), "tok_col_stats")
         mean = sums[0] / R
-        var = (sums[1] / R - mean * mean).clamp_min_(0.0)
+        var = sums[1] / R          # centred squares (hpfg_tok_col_stats): no E[x^2] - mean^2 to cancel
         rstd = torch.rsqrt(var + eps)
         y = torch.empty_like(xc)
         m = None if mask is None else mask.reshape(B, C_).float().contiguous()

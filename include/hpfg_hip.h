@@ -524,6 +524,8 @@ int hpfg_col2im_nhwc(const float* dcols, float* dx, int B, int H, int W, int C, 
 int hpfg_linear_wgrad(const float* dy, const float* x, float* dw, float* partials /* [hpfg_linear_wgrad_splits()][N][K] */, long R, int N, int K,
                       void* stream);
 int hpfg_linear_wgrad_splits(long R, int N, int K);
+/* per-channel batch statistics of tokens x [R][C]: sums[0][c] = sum_r x, sums[1][c] = sum_r (x - mean_c)^2 (centred: the biased variance
+ * is sums[1] / R whatever the mean is) */
 int hpfg_tok_col_stats(const float* x, long R, int C, float* partials /* [hpfg_tok_stat_blocks(R)][2][C] */, float* sums /* [2][C] */, void* stream);
 int hpfg_tok_stat_blocks(long R);
 int hpfg_bnrelu_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* mask, float inv_keep,

@@ -703,3 +703,185 @@ def pool_epilogue_source(seed, N, H, W, C_):
     a, mag = _act64(s["z"], s["tab"][L.BN_SCALE], s["tab"][L.BN_SHIFT])
     s["first"] = pool_argmax(a, 3.0 * U24 * mag)
     return s
+
+
+# ---- canaries around device outputs (tests/test_gpu_optim.py, tests/test_gpu_tokens_edges.py) -----------------------------------------
+PAD = 67                         # elements allocated past n: no launch may touch them
+NAN_BITS = 0x7FC0BEEF            # a quiet NaN with a payload: x != x, so only a comparison of the bits shows that it was left alone
+
+
+def padded(a, n_fill=None, dev="cuda:0"):
+    """Device buffer of len(a) + PAD floats: `a`, then (from n_fill on, default len(a)) the NaN pattern."""
+    t = torch.full((len(a) + PAD,), NAN_BITS, dtype=torch.int32, device=dev).view(torch.float32)
+    k = len(a) if n_fill is None else n_fill
+    t[:k] = torch.tensor(np.asarray(a[:k])).to(dev)          # (a copy: the shared inputs are read-only arrays)
+    return t
+
+
+def bits_kept(t, start):
+    return bool((t[start:].view(torch.int32) == NAN_BITS).all())
+
+
+def canary_out(n, dev="cuda:0"):
+    """n + PAD floats, all of them the NaN pattern: an output buffer a launch has to fill up to n and leave alone behind n."""
+    return torch.full((n + PAD,), NAN_BITS, dtype=torch.int32, device=dev).view(torch.float32)
+
+
+def canary_ok(t, n):
+    """(every one of the first n floats was written, the tail kept its bits)"""
+    return not bool((t[:n].view(torch.int32) == NAN_BITS).any()), bits_kept(t, n)
+
+
+# ---- float64 laws of the token-layout kernels (csrc/tokens.hip; reference model/segformer.py, model/swinunet.py) -----------------------
+# Plain restatements of the operations' definitions on torch double tensors, NHWC / [rows, C] like the kernels' buffers.
+# tests/test_tokens_laws_host.py holds each against torch's own float64 op and autograd.
+def chan_affine(shape, seed, gen=None):
+    """N(0,1) values with a per-channel (last axis) scale in [0.25, 4] and offset in [-3, 3]: float32."""
+    g = gen or torch.Generator().manual_seed(seed)
+    C_ = shape[-1]
+    sc = 0.25 * 16.0 ** torch.rand(C_, generator=g)
+    off = 6.0 * torch.rand(C_, generator=g) - 3.0
+    return (torch.randn(*shape, generator=g) * sc + off).float()
+
+
+def bound_8x(ref64, t32, margin=8.0):
+    """The tolerance rule of the float64 tests: `margin` x the largest error torch's own float32 CPU result `t32` makes against the float64
+    law, and no less than 4 units in the last place (float32) of the largest magnitude of the law."""
+    ref64 = ref64.double()
+    err32 = float((t32.double() - ref64).abs().max()) if ref64.numel() else 0.0
+    top = float(ref64.abs().max()) if ref64.numel() else 0.0
+    return max(margin * err32, 4.0 * float(np.spacing(np.float32(top))))
+
+
+def ln_f64(x, g, b, eps=1e-5):
+    """nn.LayerNorm over the last axis -> (y, mean, rstd)."""
+    x, g, b = x.double(), g.double(), b.double()
+    mean = x.mean(-1)
+    var = ((x - mean[..., None]) ** 2).mean(-1)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    return (x - mean[..., None]) * rstd[..., None] * g + b, mean, rstd
+
+
+def ln_bwd_f64(x, dy, g, eps=1e-5):
+    """-> (dx, dgamma, dbeta) of ln_f64."""
+    x, dy, g = x.double(), dy.double(), g.double()
+    _, mean, rstd = ln_f64(x, g, torch.zeros_like(g), eps)
+    xh = (x - mean[..., None]) * rstd[..., None]
+    dg = dy * g
+    dx = rstd[..., None] * (dg - dg.mean(-1, keepdim=True) - xh * (dg * xh).mean(-1, keepdim=True))
+    flat = lambda t: t.reshape(-1, t.shape[-1])
+    return dx, flat(dy * xh).sum(0), flat(dy).sum(0)
+
+
+def gelu_f64(u):
+    u = u.double()
+    return 0.5 * u * (1.0 + torch.special.erf(u / np.sqrt(2.0)))
+
+
+def gelu_grad_f64(u):
+    u = u.double()
+    return 0.5 * (1.0 + torch.special.erf(u / np.sqrt(2.0))) + u * torch.exp(-0.5 * u * u) / np.sqrt(2.0 * np.pi)
+
+
+def _shift3(t, dy_, dx_):
+    """t[b, y + dy_, x + dx_, c] with zeros outside, NHWC."""
+    B, H, W, C_ = t.shape
+    p = torch.zeros(B, H + 2, W + 2, C_, dtype=t.dtype)
+    p[:, 1:H + 1, 1:W + 1] = t
+    return p[:, 1 + dy_:1 + dy_ + H, 1 + dx_:1 + dx_ + W]
+
+
+def dwconv_f64(x, w9, bias):
+    """Depthwise 3 x 3 cross-correlation, padding 1, NHWC x [B,H,W,C], w9 [9][C] (tap t = 3 (dy + 1) + dx + 1) -> pre-activation u."""
+    x, w9, bias = x.double(), w9.double(), bias.double()
+    u = bias.expand_as(x).clone()
+    for t in range(9):
+        u += w9[t] * _shift3(x, t // 3 - 1, t % 3 - 1)
+    return u
+
+
+def dwgelu_bwd_f64(x, w9, bias, dy):
+    """-> (du, dx, dw9 [9][C], dbias) of gelu(dwconv_f64)."""
+    x, w9, dy = x.double(), w9.double(), dy.double()
+    du = dy * gelu_grad_f64(dwconv_f64(x, w9, bias))
+    dx = torch.zeros_like(x)
+    dw9 = torch.zeros_like(w9)
+    for t in range(9):
+        dx += w9[t] * _shift3(du, -(t // 3 - 1), -(t % 3 - 1))
+        dw9[t] = (du * _shift3(x, t // 3 - 1, t % 3 - 1)).sum((0, 1, 2))
+    return du, dx, dw9, du.sum((0, 1, 2))
+
+
+def bilinear_matrix(n_in, n_out):
+    """[n_out, n_in] float64 weights of F.interpolate(mode="bilinear", align_corners=False) along one axis: output o reads the source
+    coordinate max(0, (o + 0.5) n_in / n_out - 0.5), its floor i0 and min(i0 + 1, n_in - 1)."""
+    m = torch.zeros(n_out, n_in, dtype=torch.float64)
+    for o in range(n_out):
+        s = max(0.0, (o + 0.5) * n_in / n_out - 0.5)
+        i0 = min(int(np.floor(s)), n_in - 1)
+        i1 = min(i0 + 1, n_in - 1)
+        m[o, i0] += 1.0 - (s - i0)
+        m[o, i1] += s - i0
+    return m
+
+
+def resize_f64(x, H, W):
+    """NHWC x [B,h,w,C] -> [B,H,W,C]."""
+    t = torch.einsum("Yy,byxc->bYxc", bilinear_matrix(x.shape[1], H), x.double())          # (one axis at a time: two plain matrix products)
+    return torch.einsum("Xx,bYxc->bYXc", bilinear_matrix(x.shape[2], W), t)
+
+
+def resize_bwd_f64(dy, h, w):
+    """The transpose of resize_f64: NHWC dy [B,H,W,C] -> [B,h,w,C]."""
+    t = torch.einsum("Yy,bYXc->byXc", bilinear_matrix(h, dy.shape[1]), dy.double())
+    return torch.einsum("Xx,byXc->byxc", bilinear_matrix(w, dy.shape[2]), t)
+
+
+def col_stats_f64(x):
+    """x [R, C] -> (sum_r x, sum_r (x - mean)^2)."""
+    x = x.double()
+    return x.sum(0), ((x - x.mean(0)) ** 2).sum(0)
+
+
+def _row_mask(mask, inv_keep, rows_per_image, R, C_):
+    if mask is None:
+        return torch.ones(R, C_, dtype=torch.float64)
+    return mask.double()[torch.arange(R) // rows_per_image] * float(np.float32(inv_keep))
+
+
+def bnrelu_f64(x, mean, rstd, gamma, beta, mask=None, inv_keep=1.0, rows_per_image=1):
+    """relu((x - mean) rstd gamma + beta) mask[row // rows_per_image] inv_keep on x [R, C] -> (y, pre-activation)."""
+    x = x.double()
+    pre = (x - mean.double()) * rstd.double() * gamma.double() + beta.double()
+    return torch.relu(pre) * _row_mask(mask, inv_keep, rows_per_image, *x.shape), pre
+
+
+def bnrelu_bwd_f64(x, dy, mean, rstd, gamma, beta, mask=None, inv_keep=1.0, rows_per_image=1):
+    """-> (dx, sum g (= dbeta), sum g xhat (= dgamma)) with g = dy mask inv_keep [pre > 0]: train-mode BatchNorm's input gradient."""
+    x = x.double()
+    R = x.shape[0]
+    xh = (x - mean.double()) * rstd.double()
+    g = torch.where(xh * gamma.double() + beta.double() > 0, dy.double() * _row_mask(mask, inv_keep, rows_per_image, *x.shape), 0.0)
+    s1, s2 = g.sum(0), (g * xh).sum(0)
+    return gamma.double() * rstd.double() * (g - s1 / R - xh * s2 / R), s1, s2
+
+
+def patches_f64(x, k, s):
+    """im2col of a conv with kernel k, stride s, padding k // 2 over NHWC x -> [B, Ho*Wo, k*k*C], patch order (u, v, c); keeps x's dtype
+    (pure data movement)."""
+    B, H, W, C_ = x.shape
+    cols = torch.nn.functional.unfold(x.permute(0, 3, 1, 2), k, padding=k // 2, stride=s)          # [B, C*k*k, L], channel-major
+    L_ = cols.shape[-1]
+    return cols.reshape(B, C_, k * k, L_).permute(0, 3, 2, 1).reshape(B, L_, k * k * C_)
+
+
+def col2im_f64(dcols, H, W, C_, k, s):
+    """The transpose of patches_f64: [B, Ho*Wo, k*k*C] -> NHWC [B,H,W,C] in float64."""
+    B, L_, _ = dcols.shape
+    t = dcols.double().reshape(B, L_, k * k, C_).permute(0, 3, 2, 1).reshape(B, C_ * k * k, L_)
+    return torch.nn.functional.fold(t, (H, W), k, padding=k // 2, stride=s).permute(0, 2, 3, 1)
+
+
+def patch_merge_ref(x):
+    """Swin's PatchMerging gather on NHWC x: the four 2 x 2 neighbours concatenated along C (same dtype: data movement)."""
+    return torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)

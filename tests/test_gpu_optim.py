@@ -14,24 +14,10 @@ from hpfg_amd import _lib as L
 from hpfg_amd.utils import ema_alpha
 from hpfg_amd.utils.optim import FusedAdamW
 from tests.helpers import (ADAMW_CHECKED, ADAMW_HP, N_BIG_OPTIM, N_SMALL, SGD_ALPHAS, SGD_HYPER, SGD_LRS, adamw_case, adamw_errors, adamw_f32,
-                           adamw_torch, adamw_within, cosine_warmup_lrs, sgd_case, sgd_ema_f32, stream)
+                           adamw_torch, adamw_within, bits_kept as _bits_kept, cosine_warmup_lrs, padded as _padded, sgd_case, sgd_ema_f32, stream)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-PAD = 67                         # elements allocated past n: no launch may touch them
-NAN_BITS = 0x7FC0BEEF            # a quiet NaN with a payload: x != x, so only a comparison of the bits shows that it was left alone
-
-
-def _padded(a, n_fill=None):
-    """Device buffer of len(a) + PAD floats: `a`, then (from n_fill on, default len(a)) the NaN pattern."""
-    t = torch.full((len(a) + PAD,), NAN_BITS, dtype=torch.int32, device=DEV).view(torch.float32)
-    k = len(a) if n_fill is None else n_fill
-    t[:k] = torch.tensor(np.asarray(a[:k])).to(DEV)          # (a copy: the shared inputs are read-only arrays)
-    return t
-
-
-def _bits_kept(t, start):
-    return bool((t[start:].view(torch.int32) == NAN_BITS).all())
 
 
 def _same(dev_t, want, n):

@@ -138,19 +138,28 @@ def test_bn_relu_dropout(B, N, C_, use_mask):
 
 @pytest.mark.parametrize("R,N,K", [(9000, 32, 32), (20000, 64, 32), (8200, 32, 128), (10000, 256, 64), (8192, 4, 256), (9001, 160, 36)])
 def test_linear_tall_weight_gradient(R, N, K):
+    """Under both math modes: the default takes dW through hpfg_gemm_tn_bf16x3; HPFG_MATH=f32 with R >= TALL_ROWS reaches the row-split
+    hpfg_linear_wgrad this test is named after (tests/test_gpu_tokens_edges.py holds that kernel against float64 on its own)."""
+    from hpfg_amd import ops_tokens
+    assert R // 2 * 2 >= ops_tokens.TALL_ROWS
     g = torch.Generator().manual_seed(N + K)
     x, w, b = torch.randn(2, R // 2, K, generator=g), torch.randn(N, K, generator=g) * 0.2, torch.randn(N, generator=g)
     x = x[:, : R // 2]
     dy = torch.randn(2, R // 2, N, generator=g)
     xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
     F.linear(xr, wr, br).backward(dy)
-    xd, wd, bd = (t.to(DEV).requires_grad_(True) for t in (x, w, b))
-    y = linear(xd, wd, bd)
-    y.backward(dy.to(DEV))
-    scale = float(wr.grad.abs().max())
-    assert maxerr(y.detach().cpu(), F.linear(x, w, b)) < 1e-4
-    assert maxerr(xd.grad.cpu(), xr.grad) < 1e-4
-    assert maxerr(wd.grad.cpu(), wr.grad) < 2e-5 * max(1.0, scale) * 10 and maxerr(bd.grad.cpu(), br.grad) < 1e-3
+    for math in ("bf16x3", "f32"):
+        xd, wd, bd = (t.to(DEV).requires_grad_(True) for t in (x, w, b))
+        ops_tokens.MATH["mode"] = math
+        try:
+            y = linear(xd, wd, bd)
+            y.backward(dy.to(DEV))
+        finally:
+            ops_tokens.MATH["mode"] = None
+        scale = float(wr.grad.abs().max())
+        assert maxerr(y.detach().cpu(), F.linear(x, w, b)) < 1e-4
+        assert maxerr(xd.grad.cpu(), xr.grad) < 1e-4
+        assert maxerr(wd.grad.cpu(), wr.grad) < 2e-5 * max(1.0, scale) * 10 and maxerr(bd.grad.cpu(), br.grad) < 1e-3
 
 
 @pytest.mark.parametrize("B,H,W,C_,k,s", [(2, 64, 64, 1, 7, 4), (2, 16, 16, 32, 3, 2), (1, 9, 7, 64, 3, 2), (1, 224, 224, 1, 7, 4), (2, 8, 8, 160, 3, 2)])
