@@ -885,3 +885,191 @@ def col2im_f64(dcols, H, W, C_, k, s):
 def patch_merge_ref(x):
     """Swin's PatchMerging gather on NHWC x: the four 2 x 2 neighbours concatenated along C (same dtype: data movement)."""
     return torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+
+
+# ---- float64 law of the fused loss (csrc/loss.hip) and of the entropy mask (csrc/misc.hip) ------------------------------------------------
+# Written from the definitions in the header comment of csrc/loss.hip (CrossEntropyLoss(ignore_index=255), the batch-wide Dice of
+# utils/loss/diceloss.py:155-191, the softmax MSE of main.py:191 and UAMT's masked form :160-164), on NHWC tensors like the kernels' buffers.
+# tests/test_loss_laws_host.py holds it against oracle.losses_ref, F.cross_entropy and the reference's stored outputs.
+LOSS_OFF = 8                     # first Dice slot of `sums`
+LOSS_SMOOTH = 1e-5
+LOSS_K = (0.5, 0.5, 0.2, 0.7, 0.3)            # ce0, dice0, ce1, dice1, mse_w
+LOSS_K_DEAD = (0.5, 0.5, 0.0, 0.0, 0.3)       # group 1's supervised terms switched off: they must contribute nothing
+LOSS_SHAPES = ((3, 1, 24, 24), (2, 2, 40, 28))          # (N, n_lab, H, W)
+LOSS_MUTATIONS = ("ce_over_all_pixels", "z_skips_ignored", "dice_mean_over_c_minus_1", "masked_mse_without_2", "mse_count_without_c")
+LOSS_SUM_GROUPS = ("nll", "cnt", "mse", "mask", "I", "Z", "Y")
+
+
+def loss_stride(C_):
+    """class slots per I / Z / Y block of `sums`"""
+    return 4 if C_ <= 4 else 16
+
+
+def loss_nsum(C_):
+    return LOSS_OFF + 6 * loss_stride(C_)
+
+
+def loss_sum_groups(C_):
+    """{name: indices into `sums`} of the entries that share a magnitude: nll and cnt of both label groups, the MSE and the mask sum, and the
+    I, Z, Y slots of both groups (all class slots, the unused ones included)."""
+    S = loss_stride(C_)
+    blk = lambda k: [LOSS_OFF + g * 3 * S + k * S + c for g in range(2) for c in range(S)]
+    return {"nll": [0, 2], "cnt": [1, 3], "mse": [4], "mask": [5], "I": blk(0), "Z": blk(1), "Y": blk(2)}
+
+
+def loss_f64(logits, labels0, labels1, n_lab, coef, t=None, teacher_is_prob=False, t_unlab_only=False, cons_mask=None, input_is_prob=False,
+             world=1, grad_scale=1.0, dtype=torch.float64, mutation=None):
+    """The fused loss on CPU tensors of `dtype`: logits [N,H,W,C]; labels0 [n_lab,H,W], labels1 [N-n_lab,H,W] (class ids, 255 = ignore, None =
+    the group has no labels); t = the teacher's logits (or probabilities) of the whole batch or, with t_unlab_only, of the images from n_lab
+    on; cons_mask one weight per pixel of those images.  coef = (ce0, dice0, ce1, dice1, mse_w) and grad_scale as the float32 words the
+    kernels read.  -> (sums, out, dlogits): sums in the kernels' layout (loss_nsum(C) entries), out = [total, ce0, dice0, ce1, dice1, mse, 0, 0],
+    dlogits = grad_scale * d total / d logits by autograd (with input_is_prob: with respect to the probabilities, the cross-entropy held
+    constant).  dtype=torch.float32 is the float32 restatement that bound_8x measures.  mutation: one of LOSS_MUTATIONS, the mistakes the
+    tolerance has to tell from rounding."""
+    assert mutation is None or mutation in LOSS_MUTATIONS, mutation
+    x = logits.detach().to(dtype).clone().requires_grad_(True)
+    N, Hh, W, C_ = x.shape
+    S = loss_stride(C_)
+    k = [torch.tensor(f32_exact(v), dtype=dtype) for v in coef]
+    zero = torch.zeros((), dtype=dtype)
+    sums = torch.zeros(loss_nsum(C_), dtype=dtype)
+    p = x if input_is_prob else torch.softmax(x, -1)
+    lse = torch.logsumexp(x, -1)
+    cls = torch.arange(C_)
+    terms = []
+    for g, (lab, lo, hi) in enumerate(((labels0, 0, n_lab), (labels1, n_lab, N))):
+        ce, dice = zero, zero
+        if lab is not None and hi > lo:
+            tg = lab.long().reshape(hi - lo, Hh, W)
+            valid = tg < C_
+            picked = x[lo:hi].gather(-1, tg.clamp(max=C_ - 1).unsqueeze(-1)).squeeze(-1)
+            nll = torch.where(valid, lse[lo:hi] - picked, zero).sum()
+            cnt = valid.sum().to(dtype)
+            onehot = (tg.unsqueeze(-1) == cls).to(dtype)
+            pg = p[lo:hi]
+            I, Y = (pg * onehot).sum((0, 1, 2)), onehot.sum((0, 1, 2))
+            Z = (pg * pg).sum((0, 1, 2))
+            if mutation == "z_skips_ignored":
+                Z = (pg * pg * (tg != 255).to(dtype).unsqueeze(-1)).sum((0, 1, 2))
+            den = torch.tensor(float(valid.numel()), dtype=dtype) if mutation == "ce_over_all_pixels" else cnt
+            if float(cnt) > 0:
+                ce = nll / den
+            per_class = 1.0 - (2.0 * I + LOSS_SMOOTH) / (Z + Y + LOSS_SMOOTH)
+            dice = per_class.sum() / (C_ - 1) if mutation == "dice_mean_over_c_minus_1" else per_class.mean()
+            base = LOSS_OFF + g * 3 * S
+            with torch.no_grad():
+                sums[2 * g], sums[2 * g + 1] = nll, cnt
+                sums[base:base + C_], sums[base + S:base + S + C_], sums[base + 2 * S:base + 2 * S + C_] = I, Z, Y
+        if input_is_prob:
+            ce = ce.detach()
+        terms += [ce, dice]
+    mse = zero
+    if t is not None and N > n_lab:
+        q = t.detach().to(dtype)
+        if not teacher_is_prob:
+            q = torch.softmax(q, -1)
+        if not t_unlab_only:
+            q = q[n_lab:]
+        w = torch.ones(N - n_lab, Hh, W, dtype=dtype) if cons_mask is None else cons_mask.detach().to(dtype).reshape(N - n_lab, Hh, W)
+        s4, s5 = (w * ((p[n_lab:] - q) ** 2).sum(-1)).sum(), w.sum()
+        if cons_mask is not None:
+            mse = s4 / ((1.0 if mutation == "masked_mse_without_2" else 2.0) * s5 + 1e-16)
+        else:
+            mse = s4 / float((N - n_lab) * Hh * W * (1 if mutation == "mse_count_without_c" else C_) * world)
+        with torch.no_grad():
+            sums[4], sums[5] = s4, s5
+    terms.append(mse)
+    total = sum(kk * tt for kk, tt in zip(k, terms))
+    out = torch.stack([total] + terms + [zero, zero]).detach()
+    grad = torch.autograd.grad(total, x)[0] if total.requires_grad else torch.zeros_like(x)
+    return sums, out, (grad * f32_exact(grad_scale)).detach()
+
+
+@functools.lru_cache(maxsize=None)
+def loss_case(C_, N, n_lab, Hh, W, seed=0, ignored=0.05):
+    """Seeded inputs of one fused-loss case on the CPU (NHWC, computed once; read-only): logits and teacher logits = 2 * randn through
+    chan_affine's per-channel law (scale in [0.25, 4], offset in [-3, 3]); labels of the whole batch with about `ignored` of the pixels at 255,
+    one id in [C, 255) and class C - 1 never present; a 0 / 1 consistency mask over the images from n_lab on."""
+    g = torch.Generator().manual_seed(1000 * C_ + 10 * N + n_lab + seed)
+    def draw():
+        sc = 0.25 * 16.0 ** torch.rand(C_, generator=g)
+        off = 6.0 * torch.rand(C_, generator=g) - 3.0
+        return (2.0 * torch.randn(N, Hh, W, C_, generator=g) * sc + off).float()
+    logits, t_logits = draw(), draw()
+    lab = torch.randint(0, C_ - 1, (N, Hh, W), generator=g)
+    lab[torch.rand(N, Hh, W, generator=g) < ignored] = 255
+    flat = lab.view(N, -1)
+    for n in range(N):                                   # every image: the ignore value at both ends, an id in [C, 255) inside
+        flat[n, 0], flat[n, -1], flat[n, flat.shape[1] // 2] = 255, 255, C_ + 1
+    assert (C_ - 1) not in lab and 255 in lab and int(((lab >= C_) & (lab != 255)).sum()) >= N
+    mask = (torch.rand(N - n_lab, Hh, W, generator=g) < 0.6).float()
+    lab = lab.to(torch.uint8)
+    return dict(C=C_, N=N, n_lab=n_lab, H=Hh, W=W, logits=logits, t_logits=t_logits, labels0=lab[:n_lab].contiguous(),
+                labels1=lab[n_lab:].contiguous(), mask=mask)
+
+
+LOSS_MODES = ("teacher_logits", "teacher_prob_unlab", "masked", "no_teacher", "prob_input")
+
+
+def loss_mode_kwargs(case, mode, coef=LOSS_K):
+    """Keyword arguments of loss_f64 (and of the GPU tests' launcher) for one of LOSS_MODES on a loss_case:
+      teacher_logits       both label groups, teacher logits indexed like the batch (HPFG, CPS)
+      teacher_prob_unlab   teacher probabilities of the unlabelled images only (ICT's mixed prediction)
+      masked               teacher logits of the unlabelled images and the 0 / 1 mask (UAMT)
+      no_teacher           the supervised terms alone
+      prob_input           probabilities in, Dice only (DiceLoss(softmax=False))"""
+    c, nl = case, case["n_lab"]
+    kw = dict(logits=c["logits"], labels0=c["labels0"] if nl > 0 else None, labels1=c["labels1"] if nl < c["N"] else None, n_lab=nl,
+              coef=tuple(coef))
+    if mode == "teacher_logits":
+        kw.update(t=c["t_logits"])
+    elif mode == "teacher_prob_unlab":
+        kw.update(t=torch.softmax(c["t_logits"][nl:], -1), teacher_is_prob=True, t_unlab_only=True)
+    elif mode == "masked":
+        kw.update(t=c["t_logits"][nl:].contiguous(), t_unlab_only=True, cons_mask=c["mask"])
+    elif mode == "prob_input":
+        kw.update(logits=torch.softmax(c["logits"], -1), input_is_prob=True, coef=(0.0, coef[1], 0.0, coef[3], 0.0))
+    else:
+        assert mode == "no_teacher", mode
+    return kw
+
+
+def loss_mutation_active(mutation, kw):
+    """Whether the term a mutation changes takes part in the total of loss_f64(**kw)."""
+    N, nl = kw["logits"].shape[0], kw["n_lab"]
+    k = kw["coef"]
+    sup = [(kw["labels0"] is not None and nl > 0, k[0], k[1]), (kw["labels1"] is not None and nl < N, k[2], k[3])]
+    cons = kw.get("t") is not None and nl < N and k[4] != 0
+    if mutation == "ce_over_all_pixels":
+        return any(on and kce != 0 for on, kce, _ in sup) and not kw.get("input_is_prob", False)
+    if mutation in ("z_skips_ignored", "dice_mean_over_c_minus_1"):
+        return any(on and kd != 0 for on, _, kd in sup)
+    if mutation == "masked_mse_without_2":
+        return cons and kw.get("cons_mask") is not None
+    return cons and kw.get("cons_mask") is None
+
+
+def uncertainty_f64(preds, T, dtype=torch.float64):
+    """UAMT's entropy (2019_07_MICCAI_Uncertainty_Aware_ACDC.py:147-151): preds [T*S,H,W,C] logits, prediction t of image s at t*S + s ->
+    u [S,H,W] = -sum_c p log(p + 1e-6) with p the mean over t of the softmax."""
+    x = preds.to(dtype)
+    pm = torch.softmax(x, -1).reshape(T, x.shape[0] // T, *x.shape[1:]).mean(0)
+    return -(pm * torch.log(pm + 1e-6)).sum(-1)
+
+
+def uncertainty_threshold(u64):
+    """-> (threshold, gap): the midpoint of the widest gap between adjacent sorted values of u64 within the middle half of the distribution,
+    and that gap's width.  A threshold there lets the float64 reference alone decide every pixel of the mask."""
+    s = torch.sort(u64.reshape(-1).double()).values
+    n = s.numel()
+    mid = s[n // 4:n - n // 4]
+    d = mid[1:] - mid[:-1]
+    i = int(torch.argmax(d))
+    return float(0.5 * (mid[i] + mid[i + 1])), float(d[i])
+
+
+@functools.lru_cache(maxsize=None)
+def uncertainty_case(C_, T=8, S=3, Hh=16, W=24):
+    """T stochastic predictions (2 * randn logits, NHWC [T*S,H,W,C]) of S images; computed once, read-only."""
+    g = torch.Generator().manual_seed(40 + C_)
+    return (2.0 * torch.randn(T * S, Hh, W, C_, generator=g)).float()

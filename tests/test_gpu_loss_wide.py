@@ -145,7 +145,7 @@ def test_reference_fixture_nine_classes(golden_dir):
     assert maxerr(lg.grad.cpu(), ref) < 1e-7 + 1e-4 * float(ref.abs().max())
 
 
-@pytest.mark.parametrize("C_", [9, 16])
+@pytest.mark.parametrize("C_", [7, 9, 13, 16])
 def test_two_calls_are_bit_identical(C_):
     logits, tl, lab, pseudo, _ = _inputs(C_, SHAPES[0])
     res = []
