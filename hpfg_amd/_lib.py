@@ -19,7 +19,7 @@ OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP, OPT_UPDATE_PACK
 LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
 LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 141
+VERSION = 142
 RESIZE_TAPS = 36            # HPFG_RESIZE_TAPS: coefficients per output sample and axis of hpfg_resize_cubic's tap tables
 SURFACE_SEGS = 32           # HPFG_SURFACE_SEGS: surface-point segments of hpfg_surface_*, (class - 1) * 2 + side (0 = pred, 1 = gt)
 MATH_F32, MATH_BF16X3 = 0, 1
@@ -180,6 +180,9 @@ PROTOTYPES = {
     "hpfg_ln_fwd": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "hpfg_ln_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "hpfg_ln_bwd_blocks": (_i, [_l]),
+    "hpfg_ln_px_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "hpfg_ln_px_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "hpfg_ln_px_bwd_blocks": (_i, [_l]),
     "hpfg_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "hpfg_attn_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "hpfg_dwgelu_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
@@ -231,8 +234,13 @@ PROTOTYPES = {
     "hpfg_attn_window_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "hpfg_attn_window_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "hpfg_attn_window_scratch_floats": (_l, [_i, _i, _i, _i, _i, _i, _i]),
+    "hpfg_attn_window_drop_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _u32, _p, _p, _p]),
+    "hpfg_attn_window_drop_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _u32, _p, _p, _p]),
+    "hpfg_attn_window_drop_elems": (_l, [_i, _i, _i, _i, _i]),
+    "hpfg_attn_window_drop_mask": (_i, [_p, _i, _i, _i, _i, _i, _f, _u32, _p, _p]),
     "hpfg_gelu_fwd": (_i, [_p, _p, _l, _p]),
     "hpfg_gelu_bwd": (_i, [_p, _p, _p, _l, _p]),
+    "hpfg_token_dropout": (_i, [_p, _p, _l, _f, _u32, _p, _p, _p]),
     "hpfg_patch_merge_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "hpfg_patch_merge_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "hpfg_attn_fwd_hd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),

@@ -103,9 +103,66 @@ __device__ __forceinline__ void stage_win(const float* __restrict__ img, const i
   }
 }
 
+// ---- dropout of the probabilities (WindowAttention.attn_drop, reference model/swinunet.py:237): the DROP instantiations of the kernels below ------
+//   out = (P .* M / (1 - p)) V,   dP = (dO V^T) .* M / (1 - p),   dS = P .* (dP - rowsum(P .* dP)),   dV = (P .* M / (1 - p))^T dO
+// Element e = (((b nW + win) heads + h) L + l1) L + l2 with L = w^2 unpadded: the flat index of the reference's attn tensor [B nW, heads, L, L]
+// in its rolled, window-partitioned order.  keep(e) is a byte of an explicit mask in that layout or hpfg_keep(e, seed + *seed_dev, threshold) of
+// common.h, the rule of the HpfgAct dropout.  Only pairs of valid positions are looked up: the padding keys keep their exact zeros and the
+// padding queries contribute nothing, as without dropout.  DROP = false compiles to the kernels as they were.
+struct Drop {
+  const uint8_t* mask;
+  const uint32_t* seed_dev;
+  uint32_t seed, thresh;
+  float inv_keep;
+  __device__ __forceinline__ uint32_t word() const { return seed + (seed_dev ? *seed_dev : 0u); }
+  __device__ __forceinline__ float operator()(uint32_t sd, uint32_t e) const {
+    const bool keep = mask ? mask[e] != 0 : hpfg_keep(e, sd, thresh);
+    return keep ? inv_keep : 0.f;
+  }
+};
+
+// first element of the [L][L] tile of (image b, window win, head h)
+__device__ __forceinline__ uint32_t drop_base(const Win& g, int b, int nwin, int win, int h) {
+  return (uint32_t)((b * nwin + win) * g.heads + h) * (uint32_t)(g.L() * g.L());
+}
+
+// the factors of the lane's query l1 in the S^T orientation: f[t][r] for key 16 t + 4 g + r (1 outside the window's positions: p is 0 or unused there)
+__device__ __forceinline__ void drop_factors_t(const Drop& dr, uint32_t sd, uint32_t base, int l1, int L, int lane, f32x4 (&f)[4]) {
+  const int g = lane >> 4;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = 16 * t + 4 * g + r;
+      f[t][r] = l1 < L && key < L ? dr(sd, base + (uint32_t)(l1 * L + key)) : 1.f;
+    }
+}
+
+// ds_t of attn_core.h with dP masked before the row sum
 template <int D>
+__device__ __forceinline__ void ds_drop_t(const unsigned char* ldsV, const a_bf16x8 (&dh)[Geo<D>::KS], const a_bf16x8 (&dl)[Geo<D>::KS], int lane,
+                                          const f32x4 (&p)[4], const f32x4 (&f)[4], f32x4 (&dp)[4]) {
+  float delta = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    tile_t<D>(ldsV, t, dh, dl, lane, dp[t]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      dp[t][r] *= f[t][r];
+      delta += p[t][r] * dp[t][r];
+    }
+  }
+  delta += __shfl_xor(delta, 16);
+  delta += __shfl_xor(delta, 32);
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dp[t][r] = p[t][r] * (dp[t][r] - delta);
+}
+
+template <int D, bool DROP>
 __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ table, float* __restrict__ out, Win gm,
-                                                              float scale) {
+                                                              float scale, Drop dr) {
   constexpr int KS = Geo<D>::KS, DT = Geo<D>::DT, KPLANE = Geo<D>::KPLANE, TPL = Geo<D>::TPL;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * KPLANE + 2 * TPL];      // K hi | K lo | V^T hi | V^T lo
   __shared__ int tok[MK], rel[MK];
@@ -127,6 +184,12 @@ __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const float* __res
   load_row_frags<D>(img, t1 >= 0 ? t1 : HW, HW, C3, h, lane, scale, qh, ql);
   f32x4 p[4], o[DT];
   softmax_t<D>(ldsK, qh, ql, gm.L(), lane, WinTerm{rel[l1], rel, bias, gm.c0()}, p);
+  if constexpr (DROP) {
+    f32x4 f[4];
+    drop_factors_t(dr, dr.word(), drop_base(gm, b, gridDim.x, win, h), l1, gm.L(), lane, f);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) p[t] *= f[t];
+  }
   zero_tiles(o);
   mul_trn<D>(p, ldsVT, lane, o);                  // O^T[d][q]
   if (t1 >= 0) store_o<D>(out + ((long)b * HW + t1) * C + h * D + (lane >> 4) * 4, o);
@@ -147,9 +210,9 @@ __device__ __forceinline__ void bias_partial(const float* ds, const Win& g, floa
 }
 
 // dq = scale * dS K with dS = P .* (dP - rowsum(P .* dP)), dP = dO V^T (S^T orientation, one query per lane); the dS tile -> the bias partial
-template <int D>
+template <int D, bool DROP>
 __global__ __launch_bounds__(256) void attn_window_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ table, const float* __restrict__ dout,
-                                                             float* __restrict__ dqkv, float* __restrict__ part, Win gm, float scale) {
+                                                             float* __restrict__ dqkv, float* __restrict__ part, Win gm, float scale, Drop dr) {
   constexpr int KS = Geo<D>::KS, DT = Geo<D>::DT, KPLANE = Geo<D>::KPLANE, TPL = Geo<D>::TPL;
   __shared__ __attribute__((aligned(16))) unsigned char lds[4 * KPLANE + 2 * TPL];      // K hi|lo, V hi|lo (natural), K^T hi|lo
   __shared__ float dsl[MK * DSROW];
@@ -174,7 +237,13 @@ __global__ __launch_bounds__(256) void attn_window_dq_kernel(const float* __rest
   load_row_frags<D>(dout + (long)b * HW * C, t1 >= 0 ? t1 : HW, HW, C, h, lane, 1.f, dh, dl);
   f32x4 p[4], dp[4], o[DT];
   softmax_t<D>(ldsK, qh, ql, gm.L(), lane, WinTerm{rel[l1], rel, bias, gm.c0()}, p);
-  ds_t<D>(ldsV, dh, dl, lane, p, dp);              // dS^T: zero at the padding keys (p = 0) and padding queries (dO = 0)
+  if constexpr (DROP) {
+    f32x4 f[4];
+    drop_factors_t(dr, dr.word(), drop_base(gm, b, gridDim.x, win, h), l1, gm.L(), lane, f);
+    ds_drop_t<D>(ldsV, dh, dl, lane, p, f, dp);
+  } else {
+    ds_t<D>(ldsV, dh, dl, lane, p, dp);            // dS^T: zero at the padding keys (p = 0) and padding queries (dO = 0)
+  }
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -188,9 +257,9 @@ __global__ __launch_bounds__(256) void attn_window_dq_kernel(const float* __rest
 
 // dV = P^T dO, dK = scale * dS^T Q over the window's 64 query positions (S orientation: 4 queries per lane, the key on the lane), as
 // attn_mfma_dkv_kernel with two waves of 32 queries each; the sum of the two waves IS dK / dV of the window's keys.
-template <int D>
+template <int D, bool DROP>
 __global__ __launch_bounds__(128) void attn_window_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ table, const float* __restrict__ dout,
-                                                              float* __restrict__ dqkv, Win gm, float scale) {
+                                                              float* __restrict__ dqkv, Win gm, float scale, Drop dr) {
   constexpr int KS = Geo<D>::KS, DT = Geo<D>::DT, KPLANE = Geo<D>::KPLANE, QPL = Geo<D>::QPL;
   __shared__ __attribute__((aligned(16))) unsigned char lds[4 * KPLANE + 2 * 4 * QPL];      // K, V natural (hi|lo each); per wave: dO^T hi|lo, Q^T hi|lo
   static_assert(2 * MK * D * 4 <= 4 * KPLANE, "the wave reduction reuses the K / V images");
@@ -205,6 +274,7 @@ __global__ __launch_bounds__(128) void attn_window_dkv_kernel(const float* __res
   const long HW = (long)gm.H * gm.W;
   const float* img = qkv + (long)b * HW * C3;
   const float* db = dout + (long)b * HW * C;
+  const uint32_t drop_seed = DROP ? dr.word() : 0u, drop_e0 = drop_base(gm, b, gridDim.x, win, h);
   win_tables(gm, win, tid, tok, rel);
   load_bias<128>(table, gm, h, tid, bias);
   __syncthreads();
@@ -283,18 +353,25 @@ __global__ __launch_bounds__(128) void attn_window_dkv_kernel(const float* __res
       for (int o = 1; o < 16; o <<= 1) den += __shfl_xor(den, o);
       const float inv = 1.f / den;
       float delta = 0.f;
+      const bool live = base + 16 * u + 4 * g + r < L;      // padding queries contribute nothing (their q / dO were zeroed; P is not zero)
+      float fm[4];                                          // DROP: M / (1 - p) of (this query, the lane's key of tile t)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         s[u][t][r] *= inv;                                 // P
+        if constexpr (DROP) {
+          const int key = 16 * t + (lane & 15);
+          fm[t] = live && key < L ? dr(drop_seed, drop_e0 + (uint32_t)((base + 16 * u + 4 * g + r) * L + key)) : 1.f;
+          dp[u][t][r] *= fm[t];
+        }
         delta += s[u][t][r] * dp[u][t][r];
       }
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) delta += __shfl_xor(delta, o);
-      const bool live = base + 16 * u + 4 * g + r < L;      // padding queries contribute nothing (their q / dO were zeroed; P is not zero)
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         dp[u][t][r] = live ? s[u][t][r] * (dp[u][t][r] - delta) : 0.f;      // dS
         if (!live) s[u][t][r] = 0.f;
+        if constexpr (DROP) s[u][t][r] *= fm[t];           // dV takes the dropped probabilities
       }
     }
   // dV^T[d][key] += dO^T[d][q] P[q][key],  dK^T[d][key] += Q^T[d][q] dS[q][key]   (one contraction step over the wave's 32 queries)
@@ -363,9 +440,9 @@ __device__ __forceinline__ void stage_win_f32(const float* __restrict__ img, con
   }
 }
 
-template <int AD>
+template <int AD, bool DROP>
 __global__ __launch_bounds__(64) void attn_window_f32_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ table, float* __restrict__ out,
-                                                                 Win gm, float scale) {
+                                                                 Win gm, float scale, Drop dr) {
   __shared__ float ks[MK][AD + 1], vs[MK][AD + 1], sc[MK * DSROW];
   __shared__ int tok[MK], rel[MK];
   __shared__ float bias[TMAX];
@@ -397,9 +474,11 @@ __global__ __launch_bounds__(64) void attn_window_f32_fwd_kernel(const float* __
     mx = fmaxf(mx, row[j]);
   }
   float den = 0.f;
+  const uint32_t drop_seed = DROP ? dr.word() : 0u, drop_e0 = drop_base(gm, b, gridDim.x, win, h) + (uint32_t)(tid * L);
   for (int j = 0; j < L; ++j) {
-    const float e = expf(row[j] - mx);
+    float e = expf(row[j] - mx);
     den += e;
+    if constexpr (DROP) e *= dr(drop_seed, drop_e0 + j);
 #pragma unroll
     for (int c = 0; c < AD; ++c) o[c] += e * vs[j][c];
   }
@@ -410,10 +489,10 @@ __global__ __launch_bounds__(64) void attn_window_f32_fwd_kernel(const float* __
 }
 
 // phase 1, thread = query: P and dS rows into LDS, dq; phase 2, thread = key: dK = dS^T (scale q), dV = P^T dO; then the bias partial
-template <int AD>
+template <int AD, bool DROP>
 __global__ __launch_bounds__(64) void attn_window_f32_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ table,
                                                                  const float* __restrict__ dout, float* __restrict__ dqkv, float* __restrict__ part, Win gm,
-                                                                 float scale) {
+                                                                 float scale, Drop dr) {
   __shared__ float ks[MK][AD + 1], vs[MK][AD + 1], qs[MK][AD + 1], dos[MK][AD + 1], P[MK * DSROW], dS[MK * DSROW];
   __shared__ int tok[MK], rel[MK];
   __shared__ float bias[TMAX];
@@ -431,6 +510,7 @@ __global__ __launch_bounds__(64) void attn_window_f32_bwd_kernel(const float* __
   __syncthreads();
   const bool live = tid < L;
   const int t1 = live ? tok[tid] : 0;
+  const uint32_t drop_seed = DROP ? dr.word() : 0u, drop_e0 = drop_base(gm, b, gridDim.x, win, h) + (uint32_t)(tid * L);
   if (live) {
     const int rq = rel[tid];
     float* prow = P + tid * DSROW;
@@ -444,6 +524,7 @@ __global__ __launch_bounds__(64) void attn_window_f32_bwd_kernel(const float* __
         dp += dos[tid][c] * vs[j][c];
       }
       prow[j] = logit_add(d, rq, rel[j], c0, bias);
+      if constexpr (DROP) dp *= dr(drop_seed, drop_e0 + j);
       srow[j] = dp;
       mx = fmaxf(mx, prow[j]);
     }
@@ -461,7 +542,8 @@ __global__ __launch_bounds__(64) void attn_window_f32_bwd_kernel(const float* __
     for (int c = 0; c < AD; ++c) dqv[c] = 0.f;
     for (int j = 0; j < L; ++j) {
       const float pr = prow[j] * inv, ds = pr * (srow[j] - delta);
-      prow[j] = pr;
+      if constexpr (DROP) prow[j] = pr * dr(drop_seed, drop_e0 + j);      // dV takes the dropped probabilities
+      else prow[j] = pr;
       srow[j] = ds;
 #pragma unroll
       for (int c = 0; c < AD; ++c) dqv[c] += ds * ks[j][c];
@@ -499,25 +581,28 @@ bool shape_ok(int B, int H, int W, int heads, int head_dim, int window, int shif
          (math == HPFG_MATH_F32 || math == HPFG_MATH_BF16X3);
 }
 
-template <int D>
-void launch_fwd(const float* qkv, const float* table, float* out, int B, const Win& g, float scale, int math, hipStream_t st) {
+template <int D, bool DROP>
+void launch_fwd(const float* qkv, const float* table, float* out, int B, const Win& g, float scale, int math, const Drop& dr, hipStream_t st) {
   const dim3 grid(g.nwin(), g.heads, B);
-  if (math == HPFG_MATH_BF16X3) hipLaunchKernelGGL(attn_window_fwd_kernel<D>, grid, dim3(256), 0, st, qkv, table, out, g, scale);
-  else hipLaunchKernelGGL(attn_window_f32_fwd_kernel<D>, grid, dim3(64), 0, st, qkv, table, out, g, scale);
+  if (math == HPFG_MATH_BF16X3) hipLaunchKernelGGL((attn_window_fwd_kernel<D, DROP>), grid, dim3(256), 0, st, qkv, table, out, g, scale, dr);
+  else hipLaunchKernelGGL((attn_window_f32_fwd_kernel<D, DROP>), grid, dim3(64), 0, st, qkv, table, out, g, scale, dr);
 }
 
-template <int D>
+template <int D, bool DROP>
 void launch_bwd(const float* qkv, const float* table, const float* dout, float* dqkv, float* dbias, float* part, int B, const Win& g, float scale, int math,
-                hipStream_t st) {
+                const Drop& dr, hipStream_t st) {
   const dim3 grid(g.nwin(), g.heads, B);
   if (math == HPFG_MATH_BF16X3) {
-    hipLaunchKernelGGL(attn_window_dq_kernel<D>, grid, dim3(256), 0, st, qkv, table, dout, dqkv, part, g, scale);
-    hipLaunchKernelGGL(attn_window_dkv_kernel<D>, grid, dim3(128), 0, st, qkv, table, dout, dqkv, g, scale);
+    hipLaunchKernelGGL((attn_window_dq_kernel<D, DROP>), grid, dim3(256), 0, st, qkv, table, dout, dqkv, part, g, scale, dr);
+    hipLaunchKernelGGL((attn_window_dkv_kernel<D, DROP>), grid, dim3(128), 0, st, qkv, table, dout, dqkv, g, scale, dr);
   } else {
-    hipLaunchKernelGGL(attn_window_f32_bwd_kernel<D>, grid, dim3(64), 0, st, qkv, table, dout, dqkv, part, g, scale);
+    hipLaunchKernelGGL((attn_window_f32_bwd_kernel<D, DROP>), grid, dim3(64), 0, st, qkv, table, dout, dqkv, part, g, scale, dr);
   }
   hipLaunchKernelGGL(attn_window_dbias_sum_kernel, dim3((g.heads * g.T() + 63) / 64), dim3(256), 0, st, part, dbias, B * g.nwin(), g.heads, g.T());
 }
+
+// elements of the [B nW, heads, L, L] probability tensor the dropout draws over; they are indexed with 32 bits
+long drop_elems(int B, const Win& g) { return (long)B * g.nwin() * g.heads * g.L() * g.L(); }
 
 }  // namespace
 
@@ -539,8 +624,8 @@ extern "C" int hpfg_attn_window_fwd(const float* qkv, const float* bias_table, f
   HPFG_ARG_CHECK(qkv && bias_table && out && shape_ok(B, H, W, heads, head_dim, window, shift, math), ATTN_WINDOW_SHAPE_MSG, "attn_window_fwd", MK, B, H, W,
                  heads, head_dim, window, shift, math);
   const Win g{H, W, window, shift, heads};
-  if (head_dim == 32) launch_fwd<32>(qkv, bias_table, out, B, g, scale, math, (hipStream_t)stream);
-  else launch_fwd<64>(qkv, bias_table, out, B, g, scale, math, (hipStream_t)stream);
+  if (head_dim == 32) launch_fwd<32, false>(qkv, bias_table, out, B, g, scale, math, Drop{}, (hipStream_t)stream);
+  else launch_fwd<64, false>(qkv, bias_table, out, B, g, scale, math, Drop{}, (hipStream_t)stream);
   return hpfg_launch_status("attn_window_fwd");
 }
 
@@ -549,7 +634,53 @@ extern "C" int hpfg_attn_window_bwd(const float* qkv, const float* bias_table, c
   HPFG_ARG_CHECK(qkv && bias_table && dout && dqkv && dbias && scratch && shape_ok(B, H, W, heads, head_dim, window, shift, math), ATTN_WINDOW_SHAPE_MSG,
                  "attn_window_bwd", MK, B, H, W, heads, head_dim, window, shift, math);
   const Win g{H, W, window, shift, heads};
-  if (head_dim == 32) launch_bwd<32>(qkv, bias_table, dout, dqkv, dbias, scratch, B, g, scale, math, (hipStream_t)stream);
-  else launch_bwd<64>(qkv, bias_table, dout, dqkv, dbias, scratch, B, g, scale, math, (hipStream_t)stream);
+  if (head_dim == 32) launch_bwd<32, false>(qkv, bias_table, dout, dqkv, dbias, scratch, B, g, scale, math, Drop{}, (hipStream_t)stream);
+  else launch_bwd<64, false>(qkv, bias_table, dout, dqkv, dbias, scratch, B, g, scale, math, Drop{}, (hipStream_t)stream);
   return hpfg_launch_status("attn_window_bwd");
+}
+
+#define ATTN_WINDOW_DROP_MSG "%s: bad dropout args (0 <= p < 1, B nW heads L^2 < 2^32 mask elements; got p %g)"
+
+extern "C" int hpfg_attn_window_drop_fwd(const float* qkv, const float* bias_table, float* out, int B, int H, int W, int heads, int head_dim, int window,
+                                         int shift, float scale, int math, float p, uint32_t seed, const uint32_t* seed_dev, const uint8_t* mask,
+                                         void* stream) {
+  HPFG_ARG_CHECK(qkv && bias_table && out && shape_ok(B, H, W, heads, head_dim, window, shift, math), ATTN_WINDOW_SHAPE_MSG, "attn_window_drop_fwd", MK, B, H,
+                 W, heads, head_dim, window, shift, math);
+  const Win g{H, W, window, shift, heads};
+  HPFG_ARG_CHECK(p >= 0.f && p < 1.f && drop_elems(B, g) < (1L << 32), ATTN_WINDOW_DROP_MSG, "attn_window_drop_fwd", (double)p);
+  if (p == 0.f && !mask) return hpfg_attn_window_fwd(qkv, bias_table, out, B, H, W, heads, head_dim, window, shift, scale, math, stream);
+  const Drop dr{mask, seed_dev, seed, hpfg_drop_threshold(p), 1.f / (1.f - p)};
+  if (head_dim == 32) launch_fwd<32, true>(qkv, bias_table, out, B, g, scale, math, dr, (hipStream_t)stream);
+  else launch_fwd<64, true>(qkv, bias_table, out, B, g, scale, math, dr, (hipStream_t)stream);
+  return hpfg_launch_status("attn_window_drop_fwd");
+}
+
+extern "C" int hpfg_attn_window_drop_bwd(const float* qkv, const float* bias_table, const float* dout, float* dqkv, float* dbias, float* scratch, int B, int H,
+                                         int W, int heads, int head_dim, int window, int shift, float scale, int math, float p, uint32_t seed,
+                                         const uint32_t* seed_dev, const uint8_t* mask, void* stream) {
+  HPFG_ARG_CHECK(qkv && bias_table && dout && dqkv && dbias && scratch && shape_ok(B, H, W, heads, head_dim, window, shift, math), ATTN_WINDOW_SHAPE_MSG,
+                 "attn_window_drop_bwd", MK, B, H, W, heads, head_dim, window, shift, math);
+  const Win g{H, W, window, shift, heads};
+  HPFG_ARG_CHECK(p >= 0.f && p < 1.f && drop_elems(B, g) < (1L << 32), ATTN_WINDOW_DROP_MSG, "attn_window_drop_bwd", (double)p);
+  if (p == 0.f && !mask)
+    return hpfg_attn_window_bwd(qkv, bias_table, dout, dqkv, dbias, scratch, B, H, W, heads, head_dim, window, shift, scale, math, stream);
+  const Drop dr{mask, seed_dev, seed, hpfg_drop_threshold(p), 1.f / (1.f - p)};
+  if (head_dim == 32) launch_bwd<32, true>(qkv, bias_table, dout, dqkv, dbias, scratch, B, g, scale, math, dr, (hipStream_t)stream);
+  else launch_bwd<64, true>(qkv, bias_table, dout, dqkv, dbias, scratch, B, g, scale, math, dr, (hipStream_t)stream);
+  return hpfg_launch_status("attn_window_drop_bwd");
+}
+
+extern "C" long hpfg_attn_window_drop_elems(int B, int H, int W, int heads, int window) {
+  if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || window <= 0 || window * window > MK || H % window || W % window) {
+    hpfg_set_error("attn_window_drop_elems: bad args (B %d, map %d x %d, %d heads, window %d)", B, H, W, heads, window);
+    return -1;
+  }
+  return drop_elems(B, Win{H, W, window, 0, heads});
+}
+
+extern "C" int hpfg_attn_window_drop_mask(uint8_t* out, int B, int H, int W, int heads, int window, float p, uint32_t seed, const uint32_t* seed_dev,
+                                          void* stream) {
+  const long n = hpfg_attn_window_drop_elems(B, H, W, heads, window);
+  if (n < 0) return -1;
+  return hpfg_dropout_mask(out, n, p, seed, seed_dev, stream);          // the hash rule over the flat element index IS the mask
 }

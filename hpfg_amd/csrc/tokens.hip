@@ -10,17 +10,38 @@ namespace {
 
 constexpr float LN_EPS = 1e-5f;
 
-// ---- LayerNorm: one wave per row, C <= 1024, C % 4 == 0 ------------------------------------------------------------------------
+// The pixel shuffle of the Swin-UNet patch expanding (reference model/swinunet.py:85-111, rearrange 'B H W (P1 P2 C) -> B (H P1) (W P2) C') as
+// a row map: row r = (((b H + h) W + w) P + p1) P + p2 of the expand Linear's output, seen as a [B H W P^2, C] row matrix, is row
+// (b, h P + p1, w P + p2) of the [B, H P, W P, C] map.  P = 1 is the identity (plain LayerNorm).
+struct PxMap {
+  int P, H, W;
+  __device__ __forceinline__ long operator()(long r) const {
+    if (P == 1) return r;
+    const int p2 = (int)(r % P);
+    long t = r / P;
+    const int p1 = (int)(t % P);
+    t /= P;
+    const int w = (int)(t % W);
+    t /= W;
+    const int h = (int)(t % H);
+    return ((t / H * H + h) * P + p1) * ((long)W * P) + (long)w * P + p2;
+  }
+};
+
+// ---- LayerNorm: one wave per row, KQ float4 per lane (C <= 256 KQ), C % 4 == 0; y is written through the row map ------------------------
+template <int KQ>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
-                                                     float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, long rows, int C) {
+                                                     float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, long rows, int C,
+                                                     float eps, PxMap map) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* xr = x + row * C;
-  f32x4 v[4];
+  float* yr = y + map(row) * C;
+  f32x4 v[KQ];
   float s = 0.f;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < KQ; ++k) {
     const int c = (k * 64 + lane) * 4;
     v[k] = c < C ? *reinterpret_cast<const f32x4*>(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     s += v[k][0] + v[k][1] + v[k][2] + v[k][3];
@@ -30,7 +51,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   const float mu = s / (float)C;
   float q = 0.f;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < KQ; ++k) {
     const int c = (k * 64 + lane) * 4;
     if (c < C)
 #pragma unroll
@@ -38,16 +59,16 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o);
-  const float rs = rsqrtf(q / (float)C + LN_EPS);
+  const float rs = rsqrtf(q / (float)C + eps);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < KQ; ++k) {
     const int c = (k * 64 + lane) * 4;
     if (c < C) {
       const f32x4 gg = *reinterpret_cast<const f32x4*>(g + c), bb = *reinterpret_cast<const f32x4*>(b + c);
       f32x4 o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = (v[k][j] - mu) * rs * gg[j] + bb[j];
-      *reinterpret_cast<f32x4*>(y + row * C + c) = o;
+      *reinterpret_cast<f32x4*>(yr + c) = o;
     }
   }
   if (lane == 0) {
@@ -57,25 +78,28 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 }
 
 // dx per row; per-workgroup partial sums of dgamma / dbeta in part[blockIdx][2][C] (summed by ln_param_reduce_kernel in a fixed order)
+// dy is read through the row map, dx written contiguously
+template <int KQ>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ g,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ dx,
-                                                     float* __restrict__ part, long rows, int C, int rows_per_wg) {
-  __shared__ float red[4][2][1024];
+                                                     float* __restrict__ part, long rows, int C, int rows_per_wg, PxMap map) {
+  __shared__ float red[4][2][KQ * 256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  f32x4 ag[4], ab[4];
+  f32x4 ag[KQ], ab[KQ];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) ag[k] = ab[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < KQ; ++k) ag[k] = ab[k] = f32x4{0.f, 0.f, 0.f, 0.f};
   const long r0 = (long)blockIdx.x * rows_per_wg;
   for (long row = r0 + wave; row < r0 + rows_per_wg && row < rows; row += 4) {
     const float mu = mean[row], rs = rstd[row];
-    f32x4 xh[4], dg[4];
+    const float* dyr = dy + map(row) * C;
+    f32x4 xh[KQ], dg[KQ];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < KQ; ++k) {
       const int c = (k * 64 + lane) * 4;
       xh[k] = dg[k] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (c < C) {
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + row * C + c), dv = *reinterpret_cast<const f32x4*>(dy + row * C + c);
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + row * C + c), dv = *reinterpret_cast<const f32x4*>(dyr + c);
         const f32x4 gg = *reinterpret_cast<const f32x4*>(g + c);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -95,7 +119,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     }
     const float m1 = s1 / (float)C, m2 = s2 / (float)C;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < KQ; ++k) {
       const int c = (k * 64 + lane) * 4;
       if (c < C) {
         f32x4 o;
@@ -106,7 +130,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     }
   }
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
+  for (int k = 0; k < KQ; ++k) {
     const int c = (k * 64 + lane) * 4;
     if (c < C)
 #pragma unroll
@@ -126,7 +150,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
 // keep 8 of 64 lanes busy
 template <int G>
 __global__ __launch_bounds__(256) void ln_fwd_small_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
-                                                           float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, long rows, int C) {
+                                                           float* __restrict__ y, float* __restrict__ mean, float* __restrict__ rstd, long rows, int C,
+                                                           float eps, PxMap map) {
   constexpr int RW = 64 / G;
   const int lane = threadIdx.x & 63, q = lane % G, c = q * 4;
   const long row = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RW + lane / G;
@@ -143,13 +168,13 @@ __global__ __launch_bounds__(256) void ln_fwd_small_kernel(const float* __restri
     for (int j = 0; j < 4; ++j) d2 += (v[j] - mu) * (v[j] - mu);
 #pragma unroll
   for (int o = G / 2; o >= 1; o >>= 1) d2 += __shfl_xor(d2, o);
-  const float rs = rsqrtf(d2 / (float)C + LN_EPS);
+  const float rs = rsqrtf(d2 / (float)C + eps);
   if (on) {
     const f32x4 gg = *reinterpret_cast<const f32x4*>(g + c), bb = *reinterpret_cast<const f32x4*>(b + c);
     f32x4 o4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) o4[j] = (v[j] - mu) * rs * gg[j] + bb[j];
-    *reinterpret_cast<f32x4*>(y + row * C + c) = o4;
+    *reinterpret_cast<f32x4*>(y + map(row) * C + c) = o4;
     if (q == 0) {
       mean[row] = mu;
       rstd[row] = rs;
@@ -160,7 +185,7 @@ __global__ __launch_bounds__(256) void ln_fwd_small_kernel(const float* __restri
 template <int G>
 __global__ __launch_bounds__(256) void ln_bwd_small_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ g,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd, float* __restrict__ dx,
-                                                           float* __restrict__ part, long rows, int C, int rows_per_wg) {
+                                                           float* __restrict__ part, long rows, int C, int rows_per_wg, PxMap map) {
   constexpr int RW = 64 / G;
   __shared__ float red[4][2][256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, q = lane % G, c = q * 4;
@@ -177,7 +202,7 @@ __global__ __launch_bounds__(256) void ln_bwd_small_kernel(const float* __restri
     if (on) {
       const float mu = mean[row];
       rs = rstd[row];
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + row * C + c), dv = *reinterpret_cast<const f32x4*>(dy + row * C + c);
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + row * C + c), dv = *reinterpret_cast<const f32x4*>(dy + map(row) * C + c);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         xh[j] = (xv[j] - mu) * rs;
@@ -900,6 +925,20 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__
   }
 }
 
+// ---- dropout over a flat tensor (pos_drop, proj_drop, Mlp.drop of reference model/swinunet.py:130-132,241,440): y = x keep / (1 - p) ---------------
+// The keep rule of common.h with the flat element index: one hash word per four elements, so hpfg_dropout_mask(n, p, seed, seed_dev) is its
+// mask; an explicit byte mask [n] replaces the hash (any non-zero byte keeps).  The backward is the same launch on dy.
+__global__ __launch_bounds__(256) void token_dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long total4, uint32_t thresh, float inv_keep,
+                                                            uint32_t seed0, const uint32_t* __restrict__ seed_dev, const uint8_t* __restrict__ mask) {
+  const uint32_t seed = seed0 + (seed_dev ? *seed_dev : 0u), thr = mask ? 1u : thresh;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
+    f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+    const uint32_t h = mask ? reinterpret_cast<const uint32_t*>(mask)[i] : hpfg_hash32((uint32_t)i, seed);
+    drop_apply4(v, h, thr, inv_keep);
+    reinterpret_cast<f32x4*>(y)[i] = v;
+  }
+}
+
 // ---- PatchMerging.merging (reference model/swinunet.py:69-75): y[b][i][j][k C + c] = x[b][2 i + k % 2][2 j + k / 2][c], k = 0..3 --------------
 // One index map serves both directions (GATHER: y <- x, else the scatter backward dx <- dy; every element of either side is written once).
 template <bool GATHER>
@@ -924,13 +963,14 @@ inline int grid_cap(long total, int cap) {
 
 }  // namespace
 
-extern "C" int hpfg_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long rows, int C, void* stream) {
-  HPFG_ARG_CHECK(x && gamma && beta && y && mean && rstd && rows > 0 && C % 4 == 0 && C >= 4 && C <= 1024, "ln_fwd: bad args (C %% 4 == 0, C <= 1024)");
+// LayerNorm launches shared by hpfg_ln_* (eps 1e-5, identity map) and hpfg_ln_px_*: up to 1024 channels keep the four-float4 kernels
+static int ln_fwd_launch(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long rows, int C, float eps, PxMap map,
+                         hipStream_t st) {
   const int Q = C / 4;
   if (Q <= 64) {
-#define LN_FWD_SMALL(G)                                                                                                                              \
-  hipLaunchKernelGGL(ln_fwd_small_kernel<G>, dim3((unsigned)((rows + 4 * (64 / G) - 1) / (4 * (64 / G)))), dim3(256), 0, (hipStream_t)stream, x, gamma, \
-                     beta, y, mean, rstd, rows, C)
+#define LN_FWD_SMALL(G)                                                                                                                         \
+  hipLaunchKernelGGL(ln_fwd_small_kernel<G>, dim3((unsigned)((rows + 4 * (64 / G) - 1) / (4 * (64 / G)))), dim3(256), 0, st, x, gamma, beta, y, mean, \
+                     rstd, rows, C, eps, map)
     if (Q <= 8) LN_FWD_SMALL(8);
     else if (Q <= 16) LN_FWD_SMALL(16);
     else if (Q <= 32) LN_FWD_SMALL(32);
@@ -938,8 +978,15 @@ extern "C" int hpfg_ln_fwd(const float* x, const float* gamma, const float* beta
 #undef LN_FWD_SMALL
     return hpfg_launch_status("ln_fwd_small_kernel");
   }
-  hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, mean, rstd, rows, C);
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  if (Q <= 256) hipLaunchKernelGGL(ln_fwd_kernel<4>, grid, dim3(256), 0, st, x, gamma, beta, y, mean, rstd, rows, C, eps, map);
+  else hipLaunchKernelGGL(ln_fwd_kernel<6>, grid, dim3(256), 0, st, x, gamma, beta, y, mean, rstd, rows, C, eps, map);
   return hpfg_launch_status("ln_fwd_kernel");
+}
+
+extern "C" int hpfg_ln_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long rows, int C, void* stream) {
+  HPFG_ARG_CHECK(x && gamma && beta && y && mean && rstd && rows > 0 && C % 4 == 0 && C >= 4 && C <= 1024, "ln_fwd: bad args (C %% 4 == 0, C <= 1024)");
+  return ln_fwd_launch(x, gamma, beta, y, mean, rstd, rows, C, LN_EPS, PxMap{1, 1, 1}, (hipStream_t)stream);
 }
 
 extern "C" int hpfg_ln_bwd_blocks(long rows) {
@@ -947,33 +994,60 @@ extern "C" int hpfg_ln_bwd_blocks(long rows) {
   return (int)(b < 1 ? 1 : (b > 512 ? 512 : b));
 }
 
-extern "C" int hpfg_ln_bwd(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma,
-                           float* dbeta, float* partials, long rows, int C, void* stream) {
-  HPFG_ARG_CHECK(x && dy && gamma && mean && rstd && dx && dgamma && dbeta && partials && rows > 0 && C % 4 == 0 && C >= 4 && C <= 1024,
-                 "ln_bwd: bad args");
+static int ln_bwd_launch(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma,
+                         float* partials, long rows, int C, PxMap map, hipStream_t st) {
   const int nblk = hpfg_ln_bwd_blocks(rows);
   const int per = (int)((rows + nblk - 1) / nblk);
   const int Q = C / 4;
   if (Q <= 64) {
     const int G = Q <= 8 ? 8 : (Q <= 16 ? 16 : (Q <= 32 ? 32 : 64));
     const int step = 4 * (64 / G);                        // rows one workgroup sweep covers
-    const int per_s = (per + step - 1) / step * step;     // whole sweeps per workgroup
-    const int nb = (int)((rows + per_s - 1) / per_s);     // <= nblk; the unused partial rows are zeroed by the extra workgroups below
-    (void)nb;
+    const int per_s = (per + step - 1) / step * step;     // whole sweeps per workgroup; workgroups left without rows write zero partials
 #define LN_BWD_SMALL(GG) \
-  hipLaunchKernelGGL(ln_bwd_small_kernel<GG>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, dy, gamma, mean, rstd, dx, partials, rows, C, per_s)
+  hipLaunchKernelGGL(ln_bwd_small_kernel<GG>, dim3(nblk), dim3(256), 0, st, x, dy, gamma, mean, rstd, dx, partials, rows, C, per_s, map)
     if (G == 8) LN_BWD_SMALL(8);
     else if (G == 16) LN_BWD_SMALL(16);
     else if (G == 32) LN_BWD_SMALL(32);
     else LN_BWD_SMALL(64);
 #undef LN_BWD_SMALL
+  } else if (Q <= 256) {
+    hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(nblk), dim3(256), 0, st, x, dy, gamma, mean, rstd, dx, partials, rows, C, per, map);
   } else {
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, dy, gamma, mean, rstd, dx, partials, rows, C, per);
+    hipLaunchKernelGGL(ln_bwd_kernel<6>, dim3(nblk), dim3(256), 0, st, x, dy, gamma, mean, rstd, dx, partials, rows, C, per, map);
   }
   // dgamma and dbeta are adjacent halves of ONE [2][C] output: a single reduction launch
-  HPFG_ARG_CHECK(dbeta == dgamma + C, "ln_bwd: dgamma and dbeta must be the two halves of one [2][C] buffer");
-  hipLaunchKernelGGL(col_reduce_kernel, dim3(2 * C), dim3(64), 0, (hipStream_t)stream, partials, nblk, 2 * C, dgamma);
+  hipLaunchKernelGGL(col_reduce_kernel, dim3(2 * C), dim3(64), 0, st, partials, nblk, 2 * C, dgamma);
   return hpfg_launch_status("ln_bwd_kernel");
+}
+
+extern "C" int hpfg_ln_bwd(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma,
+                           float* dbeta, float* partials, long rows, int C, void* stream) {
+  HPFG_ARG_CHECK(x && dy && gamma && mean && rstd && dx && dgamma && dbeta && partials && rows > 0 && C % 4 == 0 && C >= 4 && C <= 1024,
+                 "ln_bwd: bad args");
+  HPFG_ARG_CHECK(dbeta == dgamma + C, "ln_bwd: dgamma and dbeta must be the two halves of one [2][C] buffer");
+  return ln_bwd_launch(x, dy, gamma, mean, rstd, dx, dgamma, partials, rows, C, PxMap{1, 1, 1}, (hipStream_t)stream);
+}
+
+static bool ln_px_ok(int B, int H, int W, int P, int C, float eps) {
+  return B > 0 && H > 0 && W > 0 && (P == 1 || P == 2 || P == 4) && C % 4 == 0 && C >= 4 && C <= 1536 && eps > 0.f &&
+         (long)B * H * W * P * P * C < (1L << 40);
+}
+#define LN_PX_MSG "%s: bad args (P 1, 2 or 4; C %% 4 == 0, 4 <= C <= 1536; eps > 0; got B %d, map %d x %d, P %d, C %d, or a null pointer)"
+
+extern "C" int hpfg_ln_px_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int B, int H, int W, int P, int C,
+                              float eps, void* stream) {
+  HPFG_ARG_CHECK(x && gamma && beta && y && mean && rstd && ln_px_ok(B, H, W, P, C, eps), LN_PX_MSG, "ln_px_fwd", B, H, W, P, C);
+  return ln_fwd_launch(x, gamma, beta, y, mean, rstd, (long)B * H * W * P * P, C, eps, PxMap{P, H, W}, (hipStream_t)stream);
+}
+
+extern "C" int hpfg_ln_px_bwd_blocks(long rows) { return hpfg_ln_bwd_blocks(rows); }
+
+extern "C" int hpfg_ln_px_bwd(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma,
+                              float* dbeta, float* partials, int B, int H, int W, int P, int C, void* stream) {
+  HPFG_ARG_CHECK(x && dy && gamma && mean && rstd && dx && dgamma && dbeta && partials && ln_px_ok(B, H, W, P, C, 1.f), LN_PX_MSG, "ln_px_bwd", B, H, W, P,
+                 C);
+  HPFG_ARG_CHECK(dbeta == dgamma + C, "ln_px_bwd: dgamma and dbeta must be the two halves of one [2][C] buffer");
+  return ln_bwd_launch(x, dy, gamma, mean, rstd, dx, dgamma, partials, (long)B * H * W * P * P, C, PxMap{P, H, W}, (hipStream_t)stream);
 }
 
 extern "C" int hpfg_attn_fwd_hd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, int head_dim, float scale, void* stream) {
@@ -1168,6 +1242,13 @@ extern "C" int hpfg_gelu_bwd(const float* x, const float* dy, float* dx, long n,
   HPFG_ARG_CHECK(x && dy && dx && n > 0 && n % 4 == 0, "gelu_bwd: bad args (n %% 4 == 0)");
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_cap(n / 4, 8192)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, n / 4);
   return hpfg_launch_status("gelu_bwd_kernel");
+}
+
+extern "C" int hpfg_token_dropout(const float* x, float* y, long n, float p, uint32_t seed, const uint32_t* seed_dev, const uint8_t* mask, void* stream) {
+  HPFG_ARG_CHECK(x && y && n > 0 && n % 4 == 0 && n < (1L << 32) && p >= 0.f && p < 1.f, "token_dropout: bad args (n %% 4 == 0, n < 2^32, 0 <= p < 1)");
+  hipLaunchKernelGGL(token_dropout_kernel, dim3(grid_cap(n / 4, 8192)), dim3(256), 0, (hipStream_t)stream, x, y, n / 4, hpfg_drop_threshold(p),
+                     1.f / (1.f - p), seed, seed_dev, mask);
+  return hpfg_launch_status("token_dropout_kernel");
 }
 
 extern "C" int hpfg_patch_merge_fwd(const float* x, float* y, int B, int H, int W, int C, void* stream) {

@@ -1,10 +1,13 @@
 """``build_model(args)``: the reference's string-keyed model factory (model/builder.py:14-62) for the hot-path architectures.
 
 Keys handled here: "unet" -> UNet, "unet_plus" -> UNet_Plus ("unet_lidc" is the same graph in the reference: model/unet_LIDC.py
-differs from model/unet.py by whitespace only), "segformer" -> SegFormer-B0, "segformer_plus" -> SegFormer_Plus (MiT-B1 + the projection necks; see model/segformer.py).  Every other key of the reference's factory is outside this build's scope and
+differs from model/unet.py by whitespace only), "segformer" -> SegFormer-B0, "segformer_plus" -> SegFormer_Plus (MiT-B1 + the projection necks; see model/segformer.py),
+"swinunet_plus" -> get_swinunet_plus(img_size=train_crop_size[0]) (Swin-UNet + the projection necks, the key of the reference's
+config/ccnet_swinunet_30k_224x224_ACDC.yaml; see model/swinunet.py; "swinunet" itself is still refused).  Every other key of the reference's factory is outside this build's scope and
 raises NotImplementedError exactly like an unknown key does there (builder.py:59-60).
 """
 from .segformer import SegFormer, SegFormer_Plus
+from .swinunet import get_swinunet_plus
 from .unet import UNet, UNet_Plus
 
 
@@ -17,4 +20,6 @@ def build_model(args):
         return SegFormer(image_size=args.train_crop_size, in_channels=args.in_channels, num_classes=args.num_classes)
     if args.model == "segformer_plus":
         return SegFormer_Plus(image_size=args.train_crop_size, in_channels=args.in_channels, num_classes=args.num_classes)
+    if args.model == "swinunet_plus":
+        return get_swinunet_plus(img_size=int(args.train_crop_size[0]), in_channels=args.in_channels, num_classes=args.num_classes)
     raise NotImplementedError(f"model '{args.model}' is outside the MI355X hot-path build (see DESIGN.md, scope)")

@@ -13,26 +13,94 @@ reference.  Where the work runs, forward and backward, all through ``hpfg_amd.op
   ``patch_merge`` (the 2 x 2 gather of PatchMerging and its scatter backward).
 
 Stochastic depth draws from the torch device generator; ``external_draws`` replays given draws (parity tests): a pair of [B] tensors
-(attention branch, MLP branch) on a block, a list of such pairs on a BasicBlock.  Dropout inside the blocks is refused: the reference
-never sets ``drop`` / ``attn_drop`` above zero.  The encoder / decoder assembly is not built here and ``build_model`` still refuses "swinunet".
+(attention branch, MLP branch) on a block, a list of such pairs on a BasicBlock.
+
+Dropout.  The reference's networks (``get_swinunet``, ``get_swinunet_plus``, ``get_swinunet_LIDC``) run the blocks with ``drop_rate = 0.1`` and
+``attn_drop_rate = 0.1``.  The constructors here still refuse non-zero rates unless the keyword-only ``allow_dropout=True`` is passed, which the
+encoder / decoder of ``model/swinunet.py`` do: ``attn_drop`` then runs inside the window-attention kernels (``window_attention_dropout``),
+``proj_drop`` / ``Mlp.drop1`` / ``Mlp.drop2`` as ``token_dropout``.  Every site has a constant layer seed (``drop_seeds``, numbered by a
+block, a stage and a network in turn, so that no two sites under one module share one) and draws keep(e) = hash(e, layer seed + seed word);
+the forward's own copy of the network's seed word and, for tests, explicit masks come in as a ``DropState``.  A block or stage used on its
+own has no seed word: its sites differ from each other, but every forward repeats the same masks -- the word, its advance and the
+per-instance base seed belong to the networks of ``model/swinunet.py``.  Eval mode launches no dropout.  ``build_model`` still refuses
+"swinunet".
 """
 from __future__ import annotations
+
+import functools
 
 import torch
 import torch.nn as nn
 
-from ..ops_tokens import gelu, layer_norm, linear, patch_merge, residual_scale, window_attention
+from ..ops_tokens import gelu, layer_norm, linear, patch_merge, residual_scale, token_dropout, window_attention, window_attention_dropout
 
 
-def _no_dropout(who: str, **rates) -> None:
+def _no_dropout(who: str, allow: bool = False, **rates) -> None:
     for name, rate in rates.items():
-        if rate != 0.0:
-            raise ValueError(f"{who}: {name} = {rate} is not built (the HIP Swin blocks have no dropout inside; the reference leaves it at 0)")
+        if rate != 0.0 and not allow:
+            raise ValueError(f"{who}: {name} = {rate} is not built without allow_dropout=True (the Swin-UNet assembly passes it; see model/swin.py)")
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"{who}: {name} = {rate} must be in [0, 1)")
 
 
 def _only(who: str, what: str, got, want) -> None:
+    """``want`` itself, or -- for nn.LayerNorm -- functools.partial(nn.LayerNorm, eps=...) as the reference's networks build their norms."""
+    if want is nn.LayerNorm and isinstance(got, functools.partial) and got.func is nn.LayerNorm and not got.args and set(got.keywords) <= {"eps"}:
+        return
     if got is not want:
         raise ValueError(f"{who}: {what} must be {want.__name__} (the HIP kernels implement nothing else), got {got!r}")
+
+
+def norm(x, ln: nn.LayerNorm):
+    """``ln(x)`` on the HIP LayerNorm with the module's own eps."""
+    return layer_norm(x, ln.weight, ln.bias, ln.eps)
+
+
+def site_seed(k: int, base: int = 0) -> int:
+    """Layer seed of dropout site k of the network instance with base seed ``base``: a 32-bit mix of both, so that the hash streams of the
+    sites, and of the same site in two networks, are unrelated."""
+    h = (k * 0x9E3779B1 + 0x5BD1E995 + (base & 0xFFFFFFFF) * 0x85EBCA6B) & 0xFFFFFFFF
+    h = ((h ^ (h >> 15)) * 0x85EBCA6B) & 0xFFFFFFFF
+    h = ((h ^ (h >> 13)) * 0xC2B2AE35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def assign_site_seeds(module: nn.Module, first: int = 0, base: int = 0) -> int:
+    """Number the dropout sites under ``module`` in module order from ``first`` on and give each its layer seed (two per WindowAttention:
+    attn_drop, proj_drop; two per Mlp: drop1, drop2); returns the next free number."""
+    k = first
+    for m in module.modules():
+        if hasattr(m, "drop_seeds"):
+            m.drop_seeds = (site_seed(k, base), site_seed(k + 1, base))
+            k += 2
+    return k
+
+
+class DropState:
+    """What a forward hands its dropout sites: ``word``, its own one-element int32 device copy of the network's seed word (None: the layer
+    seeds alone), and ``masks``, explicit uint8 keep masks by site name relative to the module that receives the state (tests)."""
+
+    def __init__(self, word=None, masks=None):
+        self.word, self.masks = word, masks or {}
+
+    def sub(self, prefix: str) -> "DropState":
+        pre = prefix + "."
+        return DropState(self.word, {k[len(pre):]: v for k, v in self.masks.items() if k.startswith(pre)})
+
+    def mask(self, name: str, like: torch.Tensor):
+        """The explicit mask of site ``name`` on ``like``'s device, or None."""
+        m = self.masks.get(name)
+        return None if m is None else m.to(device=like.device, dtype=torch.uint8).contiguous()
+
+
+NO_DROP = DropState()
+
+
+def dropout(x, p: float, seed: int, training: bool, drop: DropState, name: str):
+    """nn.Dropout(p) of a module in train mode on the HIP token dropout; nothing is launched in eval mode or at p = 0."""
+    if p == 0.0 or not training:
+        return x
+    return token_dropout(x, p, seed, drop.word, drop.mask(name, x))
 
 
 class PatchMerging(nn.Module):
@@ -45,29 +113,34 @@ class PatchMerging(nn.Module):
 
     def forward(self, x):
         x = patch_merge(x)
-        x = layer_norm(x, self.norm.weight, self.norm.bias)
-        return linear(x, self.reduction.weight)
+        return linear(norm(x, self.norm), self.reduction.weight)
 
 
 class Mlp(nn.Module):
-    def __init__(self, in_features: int, hidden_features: int = None, out_features: int = None, act_layer=nn.GELU, drop: float = 0.):
+    def __init__(self, in_features: int, hidden_features: int = None, out_features: int = None, act_layer=nn.GELU, drop: float = 0., *,
+                 allow_dropout: bool = False):
         super().__init__()
         _only("Mlp", "act_layer", act_layer, nn.GELU)
-        _no_dropout("Mlp", drop=drop)
+        _no_dropout("Mlp", allow_dropout, drop=drop)
+        self.drop = float(drop)
+        self.drop_seeds = (site_seed(2), site_seed(3))          # drop1, drop2; an enclosing block / stage / network numbers its sites anew
         out_features = out_features or in_features
         hidden_features = hidden_features or in_features
         self.fc1 = nn.Linear(in_features, hidden_features)
         self.fc2 = nn.Linear(hidden_features, out_features)
 
-    def forward(self, x):
-        return linear(gelu(linear(x, self.fc1.weight, self.fc1.bias)), self.fc2.weight, self.fc2.bias)
+    def forward(self, x, drop: DropState = NO_DROP):
+        x = dropout(gelu(linear(x, self.fc1.weight, self.fc1.bias)), self.drop, self.drop_seeds[0], self.training, drop, "drop1")
+        return dropout(linear(x, self.fc2.weight, self.fc2.bias), self.drop, self.drop_seeds[1], self.training, drop, "drop2")
 
 
 class WindowAttention(nn.Module):
     def __init__(self, dim: int, window_size: int, num_heads: int, qkv_bias: bool = True, attn_drop: float = 0., proj_drop: float = 0.,
-                 shift: bool = False):
+                 shift: bool = False, *, allow_dropout: bool = False):
         super().__init__()
-        _no_dropout("WindowAttention", attn_drop=attn_drop, proj_drop=proj_drop)
+        _no_dropout("WindowAttention", allow_dropout, attn_drop=attn_drop, proj_drop=proj_drop)
+        self.attn_drop, self.proj_drop = float(attn_drop), float(proj_drop)
+        self.drop_seeds = (site_seed(0), site_seed(1))          # attn_drop, proj_drop; an enclosing block / stage / network numbers its sites anew
         self.window_size = window_size
         self.num_heads = num_heads
         self.scale = (dim // num_heads) ** -0.5
@@ -84,24 +157,33 @@ class WindowAttention(nn.Module):
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
         self.proj = nn.Linear(dim, dim)
 
-    def forward(self, x):
+    def forward(self, x, drop: DropState = NO_DROP):
         qkv = linear(x, self.qkv.weight, self.qkv.bias)
-        a = window_attention(qkv, self.relative_position_bias_table, self.num_heads, self.window_size, self.shift_size, self.scale)
-        return linear(a, self.proj.weight, self.proj.bias)
+        if self.attn_drop == 0.0 or not self.training:
+            a = window_attention(qkv, self.relative_position_bias_table, self.num_heads, self.window_size, self.shift_size, self.scale)
+        else:          # the mask is in the reference's attn layout [B nW, heads, L, L] (rolled, window-partitioned order)
+            a = window_attention_dropout(qkv, self.relative_position_bias_table, self.num_heads, self.window_size, self.shift_size, self.scale,
+                                         self.attn_drop, self.drop_seeds[0], drop.word, drop.mask("attn_drop", qkv))
+        # proj_drop acts on the un-partitioned map here (proj commutes with window reverse and the roll back), so its explicit mask is in map
+        # order: the reference's mask after window reverse + roll back
+        return dropout(linear(a, self.proj.weight, self.proj.bias), self.proj_drop, self.drop_seeds[1], self.training, drop, "proj_drop")
 
 
 class SwinTransformerBlock(nn.Module):
     def __init__(self, dim, num_heads, window_size=7, shift=False, mlp_ratio=4., qkv_bias=True, drop=0., attn_drop=0., drop_path=0.,
-                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, *, allow_dropout: bool = False):
         super().__init__()
         _only("SwinTransformerBlock", "norm_layer", norm_layer, nn.LayerNorm)
-        _no_dropout("SwinTransformerBlock", drop=drop, attn_drop=attn_drop)
+        _no_dropout("SwinTransformerBlock", allow_dropout, drop=drop, attn_drop=attn_drop)
         self.norm1 = norm_layer(dim)
-        self.attn = WindowAttention(dim, window_size=window_size, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop, shift=shift)
+        self.attn = WindowAttention(dim, window_size=window_size, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop, shift=shift,
+                                    allow_dropout=allow_dropout)
         self.dpr = float(drop_path)
         self.norm2 = norm_layer(dim)
-        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop, allow_dropout=allow_dropout)
         self.external_draws = None        # (attention-branch draw, MLP-branch draw), each [B]: replay given uniform draws (tests)
+        self.external_masks = None        # {"attn.attn_drop", "attn.proj_drop", "mlp.drop1", "mlp.drop2": uint8 keep mask}: replay given masks (tests)
+        assign_site_seeds(self)
 
     def _keep_scale(self, batch, draw, device):
         """Per-sample factor of a residual branch (DropPath, swinunet.py:9-24): floor(keep + U) / keep, or None when nothing is dropped."""
@@ -111,21 +193,23 @@ class SwinTransformerBlock(nn.Module):
         r = torch.rand((batch,), dtype=torch.float32, device=device) if draw is None else draw.to(device).reshape(batch).float()
         return (kp + r).floor() / kp
 
-    def forward(self, x, draws=None):
+    def forward(self, x, draws=None, drop: DropState = None):
         if not x.is_cuda:
             raise RuntimeError("hpfg_amd.SwinTransformerBlock runs on the GPU only: its LayerNorm / window-attention / GELU kernels have no CPU fallback")
         d = draws if draws is not None else (self.external_draws if self.external_draws is not None else (None, None))
+        if drop is None:
+            drop = NO_DROP if self.external_masks is None else DropState(None, self.external_masks)
         B = x.shape[0]
-        a = self.attn(layer_norm(x, self.norm1.weight, self.norm1.bias))
+        a = self.attn(norm(x, self.norm1), drop.sub("attn"))
         x = residual_scale(x, a, self._keep_scale(B, d[0], x.device))
-        m = self.mlp(layer_norm(x, self.norm2.weight, self.norm2.bias))
+        m = self.mlp(norm(x, self.norm2), drop.sub("mlp"))
         return residual_scale(x, m, self._keep_scale(B, d[1], x.device))
 
 
 class BasicBlock(nn.Module):
     def __init__(self, index: int, embed_dim: int = 96, window_size: int = 7, depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24),
                  mlp_ratio: float = 4., qkv_bias: bool = True, drop_rate: float = 0., attn_drop_rate: float = 0., drop_path: float = 0.1,
-                 norm_layer=nn.LayerNorm, patch_merging: bool = True):
+                 norm_layer=nn.LayerNorm, patch_merging: bool = True, *, allow_dropout: bool = False):
         super().__init__()
         depth = depths[index]
         dim = embed_dim * 2 ** index
@@ -133,14 +217,16 @@ class BasicBlock(nn.Module):
         rates = dpr[sum(depths[:index]):sum(depths[:index + 1])]
         self.blocks = nn.ModuleList([
             SwinTransformerBlock(dim=dim, num_heads=num_heads[index], window_size=window_size, shift=i % 2 == 1, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
-                                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=rates[i], norm_layer=norm_layer)
+                                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=rates[i], norm_layer=norm_layer, allow_dropout=allow_dropout)
             for i in range(depth)])
         self.downsample = PatchMerging(dim=dim, norm_layer=norm_layer) if patch_merging else None
         self.external_draws = None        # one (attention, MLP) pair of [B] draws per block
+        assign_site_seeds(self)          # the blocks of a stage draw different masks
 
-    def forward(self, x):
+    def forward(self, x, drop: DropState = NO_DROP, draws=None):
+        draws = draws if draws is not None else self.external_draws
         for i, layer in enumerate(self.blocks):
-            x = layer(x, None if self.external_draws is None else self.external_draws[i])
+            x = layer(x, None if draws is None else draws[i], drop.sub(f"blocks.{i}"))
         if self.downsample is not None:
             x = self.downsample(x)
         return x

@@ -59,9 +59,130 @@ class _LayerNorm(torch.autograd.Function):
         return dx, dg, db
 
 
-def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
-    """nn.LayerNorm(C) with eps 1e-5 over the last dimension."""
-    return _LayerNorm.apply(x, gamma, beta)
+LN_PX_MAX_C, LN_PX_FACTORS = 1536, (1, 2, 4)          # what hpfg_ln_px_fwd / _bwd are built for
+
+
+class _LayerNormPx(torch.autograd.Function):
+    """hpfg_ln_px_fwd / _bwd: LayerNorm with eps as an argument whose rows are written through the pixel shuffle of a patch expanding."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, P, eps):
+        lib = L.load()
+        xc = x.contiguous().float()
+        C_ = gamma.numel()
+        if P == 1:          # the identity map needs a row count only: any shape [.., C]
+            B, H, W = 1, 1, xc.numel() // C_
+            y = torch.empty_like(xc)
+        else:
+            H, W = xc.shape[-3], xc.shape[-2]
+            B = xc.numel() // (H * W * P * P * C_)
+            y = torch.empty(*xc.shape[:-3], H * P, W * P, C_, dtype=torch.float32, device=x.device)
+        mean = torch.empty(B * H * W * P * P, dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        L.check(lib.hpfg_ln_px_fwd(L.ptr(xc), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(mean), L.ptr(rstd), B, H, W, P, C_, eps, _st(x)), "ln_px_fwd")
+        ctx.save_for_backward(xc, gamma, mean, rstd)
+        ctx.geo = (B, H, W, P, C_)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.load()
+        x, gamma, mean, rstd = ctx.saved_tensors
+        B, H, W, P, C_ = ctx.geo
+        dyc = dy.contiguous()
+        dx = torch.empty_like(x)
+        dgb = torch.empty(2, C_, dtype=torch.float32, device=x.device)          # [dgamma ; dbeta]: one reduction launch fills both
+        part = torch.empty(lib.hpfg_ln_px_bwd_blocks(mean.numel()) * 2 * C_, dtype=torch.float32, device=x.device)
+        L.check(lib.hpfg_ln_px_bwd(L.ptr(x), L.ptr(dyc), L.ptr(gamma), L.ptr(mean), L.ptr(rstd), L.ptr(dx), L.ptr(dgb[0]), L.ptr(dgb[1]), L.ptr(part),
+                                   B, H, W, P, C_, _st(x)), "ln_px_bwd")
+        return dx, dgb[0], dgb[1], None, None
+
+
+def _ln_px_args(who, x, gamma, beta, C_, eps):
+    if C_ % 4 or not 4 <= C_ <= LN_PX_MAX_C:
+        raise ValueError(f"{who}: C = {C_} is not built; the LayerNorm kernels take C % 4 == 0, 4 <= C <= {LN_PX_MAX_C}")
+    if gamma.numel() != C_ or beta.numel() != C_:
+        raise ValueError(f"{who}: gamma / beta must have C = {C_} elements, got {gamma.numel()} / {beta.numel()}")
+    if not eps > 0.0:
+        raise ValueError(f"{who}: eps = {eps} must be positive")
+    _need_gpu(x, who)
+
+
+def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """nn.LayerNorm(C, eps) over the last dimension.  eps 1e-5 with C <= 1024 is hpfg_ln_fwd as before; any other eps and 1024 < C <= 1536 go
+    through hpfg_ln_px_fwd with the identity row map (the same bits where both apply)."""
+    if eps == 1e-5 and x.shape[-1] <= 1024:
+        return _LayerNorm.apply(x, gamma, beta)
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"layer_norm: x {tuple(x.shape)} must be a non-empty [.., C]")
+    _ln_px_args("layer_norm", x, gamma, beta, x.shape[-1], eps)
+    return _LayerNormPx.apply(x, gamma, beta, 1, float(eps))
+
+
+def expand_layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, factor: int, eps: float = 1e-5) -> torch.Tensor:
+    """rearrange(x, 'B H W (P1 P2 C) -> B (H P1) (W P2) C') followed by nn.LayerNorm(C, eps), in one pass over x (PatchExpanding /
+    FinalPatchExpanding of the Swin-UNet after their Linear): x [B,H,W,P*P*C] -> [B,H*P,W*P,C], P = factor in LN_PX_FACTORS."""
+    if factor not in LN_PX_FACTORS:
+        raise ValueError(f"expand_layer_norm: factor {factor} is not built; the kernels take {LN_PX_FACTORS}")
+    if x.dim() != 4 or x.shape[-1] % (factor * factor):
+        raise ValueError(f"expand_layer_norm: x {tuple(x.shape)} must be [B, H, W, {factor * factor} C]")
+    _ln_px_args("expand_layer_norm", x, gamma, beta, x.shape[-1] // (factor * factor), eps)
+    return _LayerNormPx.apply(x, gamma, beta, int(factor), float(eps))
+
+
+def _drop_args(who, p, seed_dev, mask, n):
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{who}: p = {p} must be in [0, 1)")
+    if n >= 1 << 32:
+        raise ValueError(f"{who}: {n} mask elements; the dropout hash indexes them with 32 bits")
+    if seed_dev is not None and (seed_dev.dtype != torch.int32 or seed_dev.numel() != 1 or not seed_dev.is_cuda):
+        raise ValueError(f"{who}: seed_dev must be one int32 word on the device")
+    if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != n or not mask.is_cuda or not mask.is_contiguous()):
+        raise ValueError(f"{who}: mask must be a contiguous uint8 device tensor of {n} elements, got {mask.dtype} {tuple(mask.shape)}")
+
+
+class _TokenDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, seed, seed_dev, mask):
+        xc = x.contiguous().float()
+        y = torch.empty_like(xc)
+        L.check(L.load().hpfg_token_dropout(L.ptr(xc), L.ptr(y), xc.numel(), p, seed, L.ptr(seed_dev), L.ptr(mask), _st(x)), "token_dropout")
+        ctx.args = (p, seed, seed_dev, mask)          # seed_dev is the forward's own copy of the seed word: a later forward does not change it
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        p, seed, seed_dev, mask = ctx.args
+        dyc = dy.contiguous()
+        dx = torch.empty_like(dyc)
+        L.check(L.load().hpfg_token_dropout(L.ptr(dyc), L.ptr(dx), dyc.numel(), p, seed, L.ptr(seed_dev), L.ptr(mask), _st(dy)), "token_dropout (backward)")
+        return dx, None, None, None, None
+
+
+def token_dropout(x: torch.Tensor, p: float, seed: int = 0, seed_dev=None, mask=None) -> torch.Tensor:
+    """nn.Dropout(p) in train mode over a flat fp32 tensor: y = x * keep / (1 - p).  keep is the hash rule of hpfg_dropout_mask(n, p, seed,
+    seed_dev) (``dropout_mask`` below) or an explicit uint8 mask of x's element count; the count must be a multiple of 4."""
+    if x.numel() == 0 or x.numel() % 4:
+        raise ValueError(f"token_dropout: {x.numel()} elements; the kernel moves 4 floats per lane, so the count must be a positive multiple of 4")
+    _drop_args("token_dropout", p, seed_dev, mask, x.numel())
+    _need_gpu(x, "token_dropout")
+    return _TokenDropout.apply(x, float(p), int(seed) & 0xFFFFFFFF, seed_dev, mask)
+
+
+def dropout_mask(n: int, p: float, seed: int, seed_dev=None, device="cuda") -> torch.Tensor:
+    """The keep mask (uint8 [n]) of the hash rule: element i is kept iff hpfg_keep(i, seed + *seed_dev, threshold(p))."""
+    _drop_args("dropout_mask", p, seed_dev, None, n)
+    out = torch.empty(n, dtype=torch.uint8, device=device)
+    L.check(L.load().hpfg_dropout_mask(L.ptr(out), n, float(p), int(seed) & 0xFFFFFFFF, L.ptr(seed_dev), _st(out)), "dropout_mask")
+    return out
+
+
+def seed_word_add(word: torch.Tensor, v: int = 1) -> None:
+    """*word = (*word + v) & 0x7fffffff on the stream (hpfg_word_add): the advance of a network's dropout seed word; captured in a hipGraph it
+    makes every replay draw new masks."""
+    if word.dtype != torch.int32 or word.numel() != 1 or not word.is_cuda:
+        raise ValueError("seed_word_add: the seed word must be one int32 on the device")
+    L.check(L.load().hpfg_word_add(L.ptr(word), int(v), _st(word)), "word_add")
 
 
 HEAD_DIMS, MAX_KEYS = (32, 64), 64          # what csrc/attn.hip and the exact-fp32 kernels of csrc/tokens.hip are built for
@@ -230,30 +351,105 @@ class _WindowAttention(torch.autograd.Function):
         return dqkv, dtable, None, None, None, None
 
 
+def _window_args(who, qkv, bias_table, heads, window, shift):
+    if qkv.dim() != 4 or qkv.shape[-1] % 3:
+        raise ValueError(f"{who}: qkv {tuple(qkv.shape)} must be [B, H, W, 3 C]")
+    B, H, W, C3 = qkv.shape
+    C_ = C3 // 3
+    if window < 1 or window * window > MAX_WINDOW_KEYS:
+        raise ValueError(f"{who}: a {window} x {window} window has {window * window} keys; the window kernels take at most "
+                         f"{MAX_WINDOW_KEYS} keys (window <= 8)")
+    if H != W:
+        raise ValueError(f"{who}: the map must be square (H == W), got {H} x {W}")
+    if H % window or W % window:
+        raise ValueError(f"{who}: map sides {H} x {W} must be divisible by the window {window}")
+    if heads < 1 or C_ % heads or C_ // heads not in HEAD_DIMS:
+        raise ValueError(f"{who}: head dim {C_}/{heads} is not built; the HIP attention kernels exist for head dims {HEAD_DIMS}")
+    if shift not in (0, window // 2):
+        raise ValueError(f"{who}: shift {shift} must be 0 or window // 2 = {window // 2}")
+    if tuple(bias_table.shape) != ((2 * window - 1) ** 2, heads):
+        raise ValueError(f"{who}: bias_table {tuple(bias_table.shape)} must be [(2 window - 1)^2 = {(2 * window - 1) ** 2}, heads = {heads}]")
+    _need_gpu(qkv, who)
+
+
 def window_attention(qkv: torch.Tensor, bias_table: torch.Tensor, heads: int, window: int, shift: int, scale: float) -> torch.Tensor:
     """softmax(scale q k^T + relative-position bias + shifted-window mask) v inside window x window windows of the token map rolled by
     -shift (WindowAttention.forward of a Swin block between its qkv and proj Linear).  qkv [B,H,W,3C] NHWC as the qkv Linear writes it
     (channel = t C + head d + p), bias_table [(2 window - 1)^2, heads]; returns [B,H,W,C] with every token's row where the token is.
     window^2 <= MAX_WINDOW_KEYS, H == W divisible by window, head dim C / heads in HEAD_DIMS, shift 0 or window // 2."""
-    if qkv.dim() != 4 or qkv.shape[-1] % 3:
-        raise ValueError(f"window_attention: qkv {tuple(qkv.shape)} must be [B, H, W, 3 C]")
-    B, H, W, C3 = qkv.shape
-    C_ = C3 // 3
-    if window < 1 or window * window > MAX_WINDOW_KEYS:
-        raise ValueError(f"window_attention: a {window} x {window} window has {window * window} keys; the window kernels take at most "
-                         f"{MAX_WINDOW_KEYS} keys (window <= 8)")
-    if H != W:
-        raise ValueError(f"window_attention: the map must be square (H == W), got {H} x {W}")
-    if H % window or W % window:
-        raise ValueError(f"window_attention: map sides {H} x {W} must be divisible by the window {window}")
-    if heads < 1 or C_ % heads or C_ // heads not in HEAD_DIMS:
-        raise ValueError(f"window_attention: head dim {C_}/{heads} is not built; the HIP attention kernels exist for head dims {HEAD_DIMS}")
-    if shift not in (0, window // 2):
-        raise ValueError(f"window_attention: shift {shift} must be 0 or window // 2 = {window // 2}")
-    if tuple(bias_table.shape) != ((2 * window - 1) ** 2, heads):
-        raise ValueError(f"window_attention: bias_table {tuple(bias_table.shape)} must be [(2 window - 1)^2 = {(2 * window - 1) ** 2}, heads = {heads}]")
-    _need_gpu(qkv, "window_attention")
+    _window_args("window_attention", qkv, bias_table, heads, window, shift)
     return _WindowAttention.apply(qkv, bias_table, int(heads), int(window), int(shift), float(scale))
+
+
+class _WindowAttentionDrop(torch.autograd.Function):
+    """_WindowAttention with dropout of the probabilities inside the kernels (hpfg_attn_window_drop_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias_table, heads, window, shift, scale, p, seed, seed_dev, mask):
+        lib = L.load()
+        qc, tc = qkv.contiguous().float(), bias_table.contiguous().float()
+        B, H, W, C3 = qc.shape
+        d = C3 // 3 // heads
+        out = torch.empty(B, H, W, C3 // 3, dtype=torch.float32, device=qkv.device)
+        ctx.math = _MATH_CODE[gemm_math()]
+        L.check(lib.hpfg_attn_window_drop_fwd(L.ptr(qc), L.ptr(tc), L.ptr(out), B, H, W, heads, d, window, shift, scale, ctx.math, p, seed, L.ptr(seed_dev),
+                                              L.ptr(mask), _st(qkv)), "attn_window_drop_fwd")
+        ctx.save_for_backward(qc, tc)
+        ctx.geo = (heads, d, window, shift, scale)
+        ctx.drop = (p, seed, seed_dev, mask)          # seed_dev is the forward's own copy of the seed word
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        qkv, table = ctx.saved_tensors
+        heads, d, window, shift, scale = ctx.geo
+        p, seed, seed_dev, mask = ctx.drop
+        B, H, W, _ = qkv.shape
+        do = dout.contiguous()
+        dqkv, dtable = torch.empty_like(qkv), torch.empty_like(table)
+        n_scr = lib.hpfg_attn_window_scratch_floats(B, H, W, heads, d, window, ctx.math)
+        if n_scr < 0:
+            L.check(-1, "attn_window_scratch_floats")
+        scratch = torch.empty(n_scr, dtype=torch.float32, device=qkv.device)
+        L.check(lib.hpfg_attn_window_drop_bwd(L.ptr(qkv), L.ptr(table), L.ptr(do), L.ptr(dqkv), L.ptr(dtable), L.ptr(scratch), B, H, W, heads, d, window,
+                                              shift, scale, ctx.math, p, seed, L.ptr(seed_dev), L.ptr(mask), _st(qkv)), "attn_window_drop_bwd")
+        return dqkv, dtable, None, None, None, None, None, None, None, None
+
+
+def window_attention_mask_elems(B: int, H: int, W: int, heads: int, window: int) -> int:
+    """Elements of the dropout mask of ``window_attention_dropout``: the reference's attn tensor [B nW, heads, window^2, window^2]."""
+    return B * (H // window) * (W // window) * heads * window ** 4
+
+
+def window_attention_dropout(qkv: torch.Tensor, bias_table: torch.Tensor, heads: int, window: int, shift: int, scale: float, p: float, seed: int = 0,
+                             seed_dev=None, mask=None) -> torch.Tensor:
+    """``window_attention`` with nn.Dropout(p) on the probabilities between the softmax and attn @ v (WindowAttention.attn_drop), inside the
+    kernels.  The keep decision of element e of the reference's attn tensor [B nW, heads, L, L] (rolled, window-partitioned order) is byte e
+    of the explicit uint8 ``mask`` or the hash rule hpfg_keep(e, seed + *seed_dev, threshold(p)) (``window_attention_drop_mask`` writes it
+    out).  p = 0 without a mask gives the bits of ``window_attention``."""
+    if qkv.dim() != 4:
+        raise ValueError(f"window_attention_dropout: qkv {tuple(qkv.shape)} must be [B, H, W, 3 C]")
+    B, H, W, _ = qkv.shape
+    if window >= 1 and H % window == 0 and W % window == 0:
+        _drop_args("window_attention_dropout", p, seed_dev, mask, window_attention_mask_elems(B, H, W, heads, window))
+    elif not 0.0 <= p < 1.0:
+        raise ValueError(f"window_attention_dropout: p = {p} must be in [0, 1)")
+    if p == 0.0 and mask is None:
+        return window_attention(qkv, bias_table, heads, window, shift, scale)
+    _window_args("window_attention_dropout", qkv, bias_table, heads, window, shift)
+    return _WindowAttentionDrop.apply(qkv, bias_table, int(heads), int(window), int(shift), float(scale), float(p), int(seed) & 0xFFFFFFFF, seed_dev, mask)
+
+
+def window_attention_drop_mask(B: int, H: int, W: int, heads: int, window: int, p: float, seed: int, seed_dev=None, device="cuda") -> torch.Tensor:
+    """The hash keep mask of ``window_attention_dropout`` in the explicit layout (uint8 [B nW, heads, L, L]), as hpfg_attn_window_drop_mask writes it."""
+    n = window_attention_mask_elems(B, H, W, heads, window)
+    _drop_args("window_attention_drop_mask", p, seed_dev, None, n)
+    L_ = window * window
+    out = torch.empty(B * (H // window) * (W // window), heads, L_, L_, dtype=torch.uint8, device=device)
+    L.check(L.load().hpfg_attn_window_drop_mask(L.ptr(out), B, H, W, heads, window, float(p), int(seed) & 0xFFFFFFFF, L.ptr(seed_dev), _st(out)),
+            "attn_window_drop_mask")
+    return out
 
 
 class _Gelu(torch.autograd.Function):

@@ -561,16 +561,23 @@ class HPFGStep(_StepBase):
         from .model.segformer import SegFormer_Plus
         from .utils import Dense_Loss
         from .utils.optim import FusedAdamW, flatten_parameters
-        plus = [isinstance(m, SegFormer_Plus) for m in (model1, model2, ema_model)]
+        from .model.swinunet import SwinUnet_Plus
+        kinds = ["SegFormer_Plus" if isinstance(m, SegFormer_Plus) else "SwinUnet_Plus" if isinstance(m, SwinUnet_Plus) else "U-Net"
+                 for m in (model1, model2, ema_model)]
+        plus = [k != "U-Net" for k in kinds]          # the token-layout networks: three SwinUnet_Plus are handled like three SegFormer_Plus
         if any(plus):
-            if not all(plus):
+            if len(set(kinds)) != 1:
+                if "SwinUnet_Plus" in kinds:
+                    raise NotImplementedError(f"HPFGStep: mixed {' / '.join(sorted(set(kinds)))} networks are not built (the three networks must be "
+                                              f"of one kind)")
                 raise NotImplementedError("HPFGStep: mixed U-Net / SegFormer_Plus networks are not built (the three networks must be of one kind)")
             if dp is not None:
-                raise NotImplementedError("HPFGStep: data parallel (dp is not None) with SegFormer_Plus networks is not built")
+                raise NotImplementedError(f"HPFGStep: data parallel (dp is not None) with {kinds[0]} networks is not built")
             for m in (model1, model2, ema_model):      # one flat parameter buffer each: the optimizer steps and both EMA updates are single kernels
                 flatten_parameters(m)
         # SegFormer_Plus draws drop-path factors and the Dropout2d mask from the torch device generator, which hands out its sequence in HOST
         # call order whatever stream the kernels run on: the forwards are then issued as main.py:152-160 calls them -- model1, model2, teacher
+        # (SwinUnet_Plus: its dropout is counter-based, but drop-path still draws from that generator)
         self.reference_call_order = all(plus)
         super().__init__(args, dp, [model1, model2], ema_model)
         if hasattr(model1, "dense_projection_high"):

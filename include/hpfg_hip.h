@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 141
+#define HPFG_VERSION 142
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -476,6 +476,17 @@ int hpfg_ln_fwd(const float* x, const float* gamma, const float* beta, float* y,
 int hpfg_ln_bwd(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta /* == dgamma + C */,
                 float* partials /* [hpfg_ln_bwd_blocks(rows)][2][C] */, long rows, int C, void* stream);
 int hpfg_ln_bwd_blocks(long rows);
+/* LayerNorm with eps as an argument, written through the pixel shuffle of the Swin-UNet patch expanding (reference model/swinunet.py:85-111:
+ * Linear, rearrange 'B H W (P1 P2 C) -> B (H P1) (W P2) C', LayerNorm(C)): x [B,H,W,P*P*C] -- the expand Linear's output, a contiguous
+ * [B*H*W*P*P, C] row matrix -- row (b,h,w,p1,p2) is normalised over C and written at row (b, h*P+p1, w*P+p2) of y [B,H*P,W*P,C]; mean / rstd
+ * [B*H*W*P*P] are kept per row of x.  The backward reads dy through the same map, writes dx contiguously (every element once) and sums
+ * dgamma / dbeta from per-workgroup partials in a fixed order.  P 1, 2 or 4 (P = 1: plain LayerNorm with eps, the norms of the Swin-UNet at
+ * 1e-6); C % 4 == 0, 4 <= C <= 1536.  With P = 1, eps = 1e-5 and C <= 1024 the bits of hpfg_ln_fwd / hpfg_ln_bwd.  Returns -1 otherwise. */
+int hpfg_ln_px_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int B, int H, int W, int P, int C, float eps,
+                   void* stream);
+int hpfg_ln_px_bwd(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx, float* dgamma,
+                   float* dbeta /* == dgamma + C */, float* partials /* [hpfg_ln_px_bwd_blocks(rows)][2][C] */, int B, int H, int W, int P, int C, void* stream);
+int hpfg_ln_px_bwd_blocks(long rows);
 /* Attention.forward :122-126 without its Linear layers: out[b,i,h,:] = softmax_j(scale * q[b,i,h,:].k[b,j,h,:]) v[b,j,h,:];
  * q [B,N,heads,32], kv [B,M,2,heads,32] (the kv Linear's output as reshaped at :120), M <= 64 keys, head dim 32 */
 int hpfg_attn_fwd(const float* q, const float* kv, float* out, int B, int N, int M, int heads, float scale, void* stream);
@@ -510,6 +521,10 @@ int hpfg_scale_rows(const float* d, const float* scale, float* out, int B, long 
  * n % 4 == 0 */
 int hpfg_gelu_fwd(const float* x, float* y, long n, void* stream);
 int hpfg_gelu_bwd(const float* x, const float* dy, float* dx, long n, void* stream);
+/* Dropout over a flat fp32 tensor (pos_drop, proj_drop, Mlp.drop of the Swin-UNet, reference model/swinunet.py:130-132,241,440): y[i] = x[i] *
+ * keep(i) / (1 - p), one hash word per four elements; keep(i) is the rule of hpfg_dropout_mask(n, p, seed, seed_dev), so that function is
+ * its mask, or byte i of an explicit mask [n] (non-zero keeps).  The backward is the same call on dy.  n % 4 == 0, n < 2^32, 0 <= p < 1. */
+int hpfg_token_dropout(const float* x, float* y, long n, float p, uint32_t seed, const uint32_t* seed_dev, const uint8_t* mask, void* stream);
 /* PatchMerging.merging (reference model/swinunet.py:69-75) on NHWC x [B,H,W,C], H and W even, C % 4 == 0: y [B,H/2,W/2,4C] with
  * y[b][i][j][k C + c] = x[b][2 i + k % 2][2 j + k / 2][c] (the reference's concat order x0, x1, x2, x3); the backward scatters dy back, every
  * element of dx written once */
@@ -630,6 +645,20 @@ int hpfg_attn_window_bwd(const float* qkv, const float* bias_table, const float*
 /* Floats of the backward's scratch (the bias-gradient partials; reference model/swinunet.py:207-248 needs none: autograd scatter-adds into the
  * table); -1 with hpfg_last_error set when hpfg_attn_window_bwd would refuse the shape. */
 long hpfg_attn_window_scratch_floats(int B, int H, int W, int heads, int head_dim, int window, int math);
+/* hpfg_attn_window_fwd / _bwd with dropout of the probabilities between the softmax and attn @ v (WindowAttention.attn_drop, reference
+ * model/swinunet.py:237):  out = (P .* M / (1 - p)) V,  dP = (dO V^T) .* M / (1 - p),  dS = P .* (dP - rowsum(P .* dP)),  dV = (P .* M / (1 - p))^T dO,
+ * the bias-table gradient from that dS.  Keep decision of element e = (((b nW + win) heads + h) L + l1) L + l2, L = window^2: the flat index of
+ * the reference's attn tensor [B nW, heads, L, L] in its rolled, window-partitioned order -- byte e of `mask` when given (non-zero keeps), else
+ * hpfg_keep(e, seed + *seed_dev, threshold(p)), the rule of the HpfgAct dropout; hpfg_attn_window_drop_mask writes that hash mask in the
+ * explicit layout, hpfg_attn_window_drop_elems is its length (-1 for a bad shape; must stay below 2^32).  p = 0 without a mask runs the
+ * kernels of hpfg_attn_window_fwd / _bwd.  Same scratch, same shapes, every element of dqkv written once, no atomics. */
+int hpfg_attn_window_drop_fwd(const float* qkv, const float* bias_table, float* out, int B, int H, int W, int heads, int head_dim, int window, int shift,
+                              float scale, int math, float p, uint32_t seed, const uint32_t* seed_dev, const uint8_t* mask, void* stream);
+int hpfg_attn_window_drop_bwd(const float* qkv, const float* bias_table, const float* dout, float* dqkv, float* dbias, float* scratch, int B, int H, int W,
+                              int heads, int head_dim, int window, int shift, float scale, int math, float p, uint32_t seed, const uint32_t* seed_dev,
+                              const uint8_t* mask, void* stream);
+long hpfg_attn_window_drop_elems(int B, int H, int W, int heads, int window);
+int hpfg_attn_window_drop_mask(uint8_t* out, int B, int H, int W, int heads, int window, float p, uint32_t seed, const uint32_t* seed_dev, void* stream);
 
 /* ---- projection necks + Dense_Loss (UNet_Plus; reference model/unet.py:120-152, utils/loss/dense_loss.py:17-40) ------------------------ */
 /* C[m,n] = act(sum_k A(m,k) B(k,n) + bias[n]) in exact fp32 on the matrix cores; A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn], C row-major
