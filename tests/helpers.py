@@ -1073,3 +1073,321 @@ def uncertainty_case(C_, T=8, S=3, Hh=16, W=24):
     """T stochastic predictions (2 * randn logits, NHWC [T*S,H,W,C]) of S images; computed once, read-only."""
     g = torch.Generator().manual_seed(40 + C_)
     return (2.0 * torch.randn(T * S, Hh, W, C_, generator=g)).float()
+
+
+# ---- float64 laws of the attention kernels (csrc/attn.hip, attn_keys.hip, attn_window.hip, the thread-per-query kernels of tokens.hip) --
+# One formula, softmax(scale q k^T + bias + mask) v with its closed-form backward, written three times over in plain torch: in float64
+# (the law), in float32 (the yardstick of HPFG_MATH=f32) and in the arithmetic the top of csrc/attn_core.h documents (the yardstick of the
+# split-bf16 kernels).  No tiles, lanes or key blocks.  tests/test_attn_laws_host.py holds the laws against float64 autograd of the
+# written-out formulas and shows that each named mutation is caught; tests/test_gpu_attn_edges.py holds the kernels against the laws.
+ATTN_MUTATIONS = ("pad_keys", "dkv_tail", "dk_no_scale")
+WINDOW_MUTATIONS = ("mask_inf", "pad_keys", "bias_transposed", "bias_scaled", "mask_edge", "roll_sign", "hw_swap")
+ATTN_IMAGE_KEYS = 64             # keys of one LDS image: what a kernel that forgot to exclude the padding keys would normalise over
+ATTN_DKV_QUERIES = 512           # queries per dK / dV workgroup (Q_PER_BLOCK of csrc/attn_core.h)
+WINDOW_MASKED = -100.0           # the reference's literal (model/swinunet.py:204), not -inf
+
+
+def _bf16_split(x):
+    """x (float32) -> hi, lo as float64: hi = bf16 round-to-nearest of x, lo = bf16 round-to-nearest of x - hi (exact in float32)."""
+    x = x.float()
+    hi = x.bfloat16().float()
+    lo = (x - hi).bfloat16().float()
+    return hi.double(), lo.double()
+
+
+def _prod3(a, b):
+    """a @ b of two float32 operands as the matrix cores form it: hi.hi + lo.hi + hi.lo (every bf16 product is exact), accumulated here
+    without rounding and rounded once to float32."""
+    ah, al = _bf16_split(a)
+    bh, bl = _bf16_split(b)
+    return (ah @ bh + al @ bh + ah @ bl).float()
+
+
+def _attn_core(q, k, v, do, scale, bias=None, mask=None, arith=torch.float64, max_subtract=True, pad_keys=0):
+    """q, do [..., Lq, d], k, v [..., Lk, d], bias / mask broadcastable to [..., Lq, Lk] -> out, lse, dq, dk, dv, dS (gradient of the logits).
+    arith: torch.float64 / torch.float32 (every operation in that type) or "split" (attn_core.h: scale folded into q, split-bf16 products
+    rounded to float32, float32 softmax, P and dS split again for the second product)."""
+    split = arith == "split"
+    dt = torch.float32 if split else arith
+    q, k, v, do = (t.to(dt) for t in (q, k, v, do))
+    mm = _prod3 if split else torch.matmul
+    T = lambda t: t.transpose(-2, -1)
+    if pad_keys:                                   # mutation: padding keys (zero rows of K and V) take part with logit 0
+        z = torch.zeros(*k.shape[:-2], pad_keys, k.shape[-1], dtype=dt)
+        k, v = torch.cat([k, z], -2), torch.cat([v, z], -2)
+    qs = q * torch.tensor(scale, dtype=dt) if split else q
+    S = mm(qs, T(k)) if split else mm(q, T(k)) * scale
+    for add in (bias, mask):
+        if add is not None:
+            add = add.to(dt)
+            if pad_keys:
+                add = torch.cat([add, torch.zeros(*add.shape[:-1], pad_keys, dtype=dt)], -1)
+            S = S + add
+    mx = S.amax(-1, keepdim=True) if max_subtract else torch.zeros_like(S[..., :1])
+    e = torch.exp(S - mx)
+    den = e.sum(-1, keepdim=True)
+    P = e * (1.0 / den) if split else e / den
+    lse = (mx + torch.log(den)).squeeze(-1)
+    out = mm(P, v)
+    dP = mm(do, T(v))
+    dS = P * (dP - (P * dP).sum(-1, keepdim=True))
+    if split:
+        dq, dk = mm(dS, k) * torch.tensor(scale, dtype=dt), mm(T(dS), qs)          # dK carries the scale through the scaled q
+    else:
+        dq, dk = mm(dS, k) * scale, mm(T(dS), q) * scale
+    dv = mm(T(P), do)
+    if pad_keys:
+        dk, dv, dS = dk[..., :-pad_keys, :], dv[..., :-pad_keys, :], dS[..., :-pad_keys]
+    return out, lse, dq, dk, dv, dS
+
+
+def attn_f64(q, kv, do, heads, d, scale, mutation=None, arith=torch.float64, max_subtract=True):
+    """softmax(scale q k^T) v per (image, head) and its gradients: q, do [B,N,heads d], kv [B,M,2 heads d] laid out [.., 2, heads, d] ->
+    out [B,N,heads d], lse [B,heads,N] (log of the softmax denominator), dq like q, dkv like kv; in `arith` like the inputs' shape."""
+    B, N, C_ = q.shape
+    M = kv.shape[1]
+    qh, dh = (t.reshape(B, N, heads, d).permute(0, 2, 1, 3) for t in (q, do))
+    k, v = kv.reshape(B, M, 2, heads, d).permute(2, 0, 3, 1, 4)
+    pad = (-M) % ATTN_IMAGE_KEYS if mutation == "pad_keys" else 0
+    out, lse, dq, dk, dv, _ = _attn_core(qh, k, v, dh, scale, arith=arith, max_subtract=max_subtract, pad_keys=pad)
+    if mutation == "dkv_tail":                     # dK / dV over the full blocks of 512 queries only
+        n = N // ATTN_DKV_QUERIES * ATTN_DKV_QUERIES
+        _, _, _, dk, dv, _ = _attn_core(qh[:, :, :n], k, v, dh[:, :, :n], scale, arith=arith)
+    if mutation == "dk_no_scale" and scale != 0:
+        dk = dk / scale
+    back = lambda t: t.permute(0, 2, 1, 3).reshape(B, N, C_)
+    return back(out), lse, back(dq), torch.stack([dk, dv]).permute(1, 3, 0, 2, 4).reshape(B, M, 2 * C_)
+
+
+def attn_split_emulation(q, kv, do, heads, d, scale):
+    """attn_f64 in the arithmetic of csrc/attn_core.h: the yardstick of the split-bf16 kernels."""
+    return attn_f64(q, kv, do, heads, d, scale, arith="split")
+
+
+def window_partition(x, w):
+    """[B,H,W,...] -> [B * nW, w * w, ...] (window_partition of the reference)"""
+    B, H, W = x.shape[:3]
+    rest = x.shape[3:]
+    k = len(rest)
+    return x.reshape(B, H // w, w, W // w, w, *rest).permute(0, 1, 3, 2, 4, *range(5, 5 + k)).reshape(B * (H // w) * (W // w), w * w, *rest)
+
+
+def window_reverse(xw, B, H, W, w):
+    C_ = xw.shape[-1]
+    return xw.reshape(B, H // w, W // w, w, w, C_).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C_)
+
+
+def window_attn_reference(qkv, table, heads, w, s, scale):
+    """WindowAttention.forward of the reference between its qkv and proj Linear, written out with the reference's own tensor operations
+    (roll, partition, index table, region image, softmax, reverse, roll back); differentiable, any H x W divisible by w."""
+    B, H, W, C3 = qkv.shape
+    C_, L_ = C3 // 3, w * w
+    d = C_ // heads
+    x = torch.roll(qkv, (-s, -s), (1, 2)) if s else qkv
+    xw = window_partition(x, w).reshape(-1, L_, 3, heads, d).permute(2, 0, 3, 1, 4)            # [3, Bn, heads, L, d]
+    q, k, v = xw[0] * scale, xw[1], xw[2]
+    a = q @ k.transpose(-2, -1)
+    l = torch.arange(L_)
+    i, j = l // w, l % w
+    idx = (i[:, None] - i[None, :] + w - 1) * (2 * w - 1) + (j[:, None] - j[None, :] + w - 1)
+    a = a + table[idx.reshape(-1)].reshape(L_, L_, heads).permute(2, 0, 1)[None]
+    if s:
+        img = torch.zeros(1, H, W, 1, dtype=qkv.dtype)
+        cnt = 0
+        for hs in (slice(0, -w), slice(-w, -s), slice(-s, None)):
+            for ws in (slice(0, -w), slice(-w, -s), slice(-s, None)):
+                img[:, hs, ws, :] = cnt
+                cnt += 1
+        mw = window_partition(img, w).reshape(-1, L_)
+        m = mw[:, None, :] - mw[:, :, None]
+        m = torch.where(m != 0, torch.full_like(m, WINDOW_MASKED), torch.zeros_like(m))
+        nW = m.shape[0]
+        a = (a.reshape(B, nW, heads, L_, L_) + m[None, :, None]).reshape(-1, heads, L_, L_)
+    o = (a.softmax(-1) @ v).transpose(1, 2).reshape(-1, L_, C_)
+    o = window_reverse(o, B, H, W, w)
+    return torch.roll(o, (s, s), (1, 2)) if s else o
+
+
+def window_tables(H, W, w, s, mutation=None):
+    """The definition as index tables: tok [nW, L] = the token y W + x at position l = i w + j of window (wy, wx) of the map rolled by -s,
+    region [nW, L] = 3 r(y') + r(x') of the rolled coordinate (r = 0 below n - w, 1 below n - s, else 2), idx [L, L] = the bias-table row of
+    (query l1, key l2)."""
+    nwy, nwx = H // w, W // w
+    win, l = torch.arange(nwy * nwx), torch.arange(w * w)
+    per_row = nwy if mutation == "hw_swap" else nwx
+    yp = (win // per_row)[:, None] * w + (l // w)[None]
+    xp = (win % per_row)[:, None] * w + (l % w)[None]
+    sh = -s if mutation == "roll_sign" else s
+    tok = ((yp + sh) % H) * W + (xp + sh) % W
+    cut = s + 1 if mutation == "mask_edge" else s
+
+    def region(p, n):
+        return (p >= n - w).long() + (p >= n - cut).long()
+    reg = 3 * region(yp, H) + region(xp, W) if s else torch.zeros_like(tok)
+    i, j = l // w, l % w
+    idx = (i[:, None] - i[None, :] + w - 1) * (2 * w - 1) + (j[:, None] - j[None, :] + w - 1)
+    return tok, reg, idx.t() if mutation == "bias_transposed" else idx
+
+
+def window_attn_f64(qkv, table, do, heads, w, s, scale, mutation=None, arith=torch.float64):
+    """Shifted-window attention and its gradients from the index tables: qkv [B,H,W,3 heads d] (channel = t heads d + head d + p),
+    table [(2w-1)^2, heads], do [B,H,W,heads d] -> out like do, dqkv like qkv, dtable like table."""
+    B, H, W, C3 = qkv.shape
+    C_, L_ = C3 // 3, w * w
+    d = C_ // heads
+    dt = torch.float32 if arith == "split" else arith
+    tok, reg, idx = window_tables(H, W, w, s, mutation)
+    nW = tok.shape[0]
+    x = qkv.reshape(B, H * W, 3, heads, d)[:, tok].permute(3, 0, 1, 4, 2, 5)                  # [3, B, nW, heads, L, d]
+    dh = do.reshape(B, H * W, heads, d)[:, tok].permute(0, 1, 3, 2, 4)
+    tab = table.to(dt) * (torch.tensor(scale, dtype=dt) if mutation == "bias_scaled" else 1.0)
+    bias = tab[idx.reshape(-1)].reshape(L_, L_, heads).permute(2, 0, 1)                       # [heads, L, L]
+    mask = None
+    if s:
+        differ = reg[:, :, None] != reg[:, None, :]
+        mask = torch.where(differ, float("-inf") if mutation == "mask_inf" else WINDOW_MASKED, 0.0).to(dt)[:, None]      # [nW, 1, L, L]
+    pad = (-L_) % ATTN_IMAGE_KEYS if mutation == "pad_keys" else 0
+    o, _, dq, dk, dv, dS = _attn_core(x[0], x[1], x[2], dh, scale, bias=bias, mask=mask, arith=arith, pad_keys=pad)
+    out, dqkv = torch.zeros(B, H * W, C_, dtype=dt), torch.zeros(B, H * W, 3, heads, d, dtype=dt)
+    out[:, tok] = o.permute(0, 1, 3, 2, 4).reshape(B, nW, L_, C_)
+    dqkv[:, tok] = torch.stack([dq, dk, dv]).permute(1, 2, 4, 0, 3, 5)
+    dtable = torch.zeros(table.shape[0], heads, dtype=dt).index_add_(0, idx.reshape(-1), dS.sum((0, 1)).permute(1, 2, 0).reshape(L_ * L_, heads))
+    if mutation == "bias_scaled":
+        dtable = dtable * scale
+    return out.reshape(B, H, W, C_), dqkv.reshape(B, H, W, C3), dtable
+
+
+def attn_tolerance(ref64, yardstick):
+    """Per output tensor: 8 x the largest error the yardstick (torch float32 on the CPU for HPFG_MATH=f32, the split-bf16 emulation for the
+    default mode) makes against the float64 law, and no less than 4 float32 ulp of the law's largest magnitude."""
+    return tuple(bound_8x(r, y) for r, y in zip(ref64, yardstick))
+
+
+ATTN_MATHS = ("f32", "bf16x3")
+ATTN_YARDSTICK = {"f32": torch.float32, "bf16x3": "split"}
+
+
+def _row_max_p(S):
+    return torch.softmax(S.double(), -1).amax(-1)
+
+
+def _attn_logits(q, kv, heads, d, scale):
+    B, N, _ = q.shape
+    M = kv.shape[1]
+    k = kv.reshape(B, M, 2, heads, d)[:, :, 0]
+    return torch.einsum("bnhd,bmhd->bhnm", q.reshape(B, N, heads, d).double(), k.double()) * scale
+
+
+def attn_inputs(family, B, N, M, heads, d, scale=None):
+    """q, kv, do (float32, fixed seed) of an input family, with the family's condition asserted in float64:
+    unit    randn: logits about N(0, 1)
+    sharp   q and k times 2 (times 2.5 above 64 keys): the median row's largest probability is at least 0.5; with N >= 128 every 16-key
+            tile and the last key hold the maximum of some row
+    offset  q[..., 0] = 16, k[..., 0] = 100 sqrt(d) / 16 in every head: +100 on every logit of a row, the softmax unchanged; every row's
+            largest logit exceeds 89, where float32 exp overflows without the max subtraction"""
+    sc = d ** -0.5 if scale is None else scale
+    C_ = heads * d
+    for attempt in range(16):                      # sharp: the first of 16 fixed seeds whose draw meets the condition
+        g = torch.Generator().manual_seed(7919 * attempt + 1000 * d + 31 * N + M + 7 * B + heads)
+        q, kv, do = torch.randn(B, N, C_, generator=g), torch.randn(B, M, 2 * C_, generator=g), torch.randn(B, N, C_, generator=g)
+        if family == "unit":
+            return q, kv, do
+        if family == "offset":
+            assert scale is None
+            q.view(B, N, heads, d)[..., 0] = 16.0
+            kv.view(B, M, 2, heads, d)[:, :, 0, :, 0] = 100.0 * d ** 0.5 / 16.0
+            S = _attn_logits(q, kv, heads, d, sc)
+            assert float(S.amax(-1).min()) > 89.0
+            return q, kv, do
+        assert family == "sharp"
+        mul = 2.0 if M <= ATTN_IMAGE_KEYS else 2.5          # over 65 .. 256 keys times 2 leaves the median at 0.42 .. 0.54: the condition decides
+        q *= mul
+        kv.view(B, M, 2, heads, d)[:, :, 0] *= mul
+        S = _attn_logits(q, kv, heads, d, sc)
+        ok = float(_row_max_p(S).median()) >= 0.5
+        if N >= 128:
+            hit = torch.zeros(M, dtype=torch.bool)
+            hit[S.argmax(-1).reshape(-1)] = True
+            ok = ok and bool(hit[M - 1]) and all(bool(hit[t:t + 16].any()) for t in range(0, M, 16))
+        if ok:
+            return q, kv, do
+    raise AssertionError(f"sharp: no draw met the condition for {(B, N, M, heads, d)}")
+
+
+@functools.lru_cache(maxsize=None)
+def attn_case(family, B, N, M, heads, d, scale=None):
+    """-> dict: inputs, scale, the float64 law `ref` = (out, lse, dq, dkv), and per math mode the yardstick's results and the tolerances.
+    Computed once per case and shared; read-only."""
+    sc = d ** -0.5 if scale is None else scale
+    q, kv, do = attn_inputs(family, B, N, M, heads, d, scale)
+    ref = attn_f64(q, kv, do, heads, d, sc)
+    yard = {m: attn_f64(q, kv, do, heads, d, sc, arith=a) for m, a in ATTN_YARDSTICK.items()}
+    return dict(q=q, kv=kv, do=do, scale=sc, ref=ref, yard=yard, tol={m: attn_tolerance(ref, y) for m, y in yard.items()})
+
+
+def _window_logits(qkv, table, heads, w, s, scale):
+    """[B, nW, heads, L, L] float64 logits (bias and mask included) of the law"""
+    B, H, W, C3 = qkv.shape
+    d, L_ = C3 // 3 // heads, w * w
+    tok, reg, idx = window_tables(H, W, w, s)
+    x = qkv.double().reshape(B, H * W, 3, heads, d)[:, tok].permute(3, 0, 1, 4, 2, 5)
+    S = (x[0] @ x[1].transpose(-2, -1)) * scale + table.double()[idx.reshape(-1)].reshape(L_, L_, heads).permute(2, 0, 1)
+    if s:
+        S = S + torch.where(reg[:, :, None] != reg[:, None, :], WINDOW_MASKED, 0.0).double()[:, None]
+    return S
+
+
+def window_inputs(family, B, H, W, w, s, heads, d, scale=None):
+    """qkv, table, do (float32, fixed seed): unit = randn; sharp = q and k times 2 (median row-max probability at least 0.5); hot = q and k
+    times 8 (logits of tens, so a masked pair at -100 still competes: its condition, that -inf for -100 moves `out` by at least four
+    tolerances, is asserted by window_case, which has the tolerances)."""
+    C_ = heads * d
+    g = torch.Generator().manual_seed(100000 * H + 1000 * W + 100 * w + 10 * s + d + B + heads)
+    qkv, do = torch.randn(B, H, W, 3 * C_, generator=g), torch.randn(B, H, W, C_, generator=g)
+    table = torch.randn((2 * w - 1) ** 2, heads, generator=g)
+    mul = {"unit": 1.0, "sharp": 2.0, "hot": 8.0}[family]
+    qkv[..., :2 * C_] *= mul
+    if family == "sharp":
+        S = _window_logits(qkv, table, heads, w, s, d ** -0.5 if scale is None else scale)
+        assert float(_row_max_p(S).median()) >= 0.5
+    return qkv, table, do
+
+
+def window_results(res):
+    """(out, dqkv, dtable) -> (out, dq, dk, dv, dtable): the window op's gradients have a tolerance each"""
+    return (res[0],) + tuple(res[1].chunk(3, -1)) + (res[2],)
+
+
+WINDOW_TENSORS = ("out", "dq", "dk", "dv", "dtable")
+
+
+@functools.lru_cache(maxsize=None)
+def window_case(family, B, H, W, w, s, heads, d, scale=None):
+    """-> dict like attn_case: `ref` = (out, dq, dk, dv, dtable) of the float64 law."""
+    sc = d ** -0.5 if scale is None else scale
+    qkv, table, do = window_inputs(family, B, H, W, w, s, heads, d, scale)
+    ref = window_results(window_attn_f64(qkv, table, do, heads, w, s, sc))
+    yard = {m: window_results(window_attn_f64(qkv, table, do, heads, w, s, sc, arith=a)) for m, a in ATTN_YARDSTICK.items()}
+    tol = {m: attn_tolerance(ref, y) for m, y in yard.items()}
+    if family == "hot" and s:                      # the family's condition: -inf in place of the literal -100 is far outside the tolerance
+        moved = window_attn_f64(qkv, table, do, heads, w, s, sc, mutation="mask_inf")[0]
+        assert float((moved - ref[0]).abs().max()) >= 4.0 * max(t[0] for t in tol.values())
+    return dict(qkv=qkv, table=table, do=do, scale=sc, ref=ref, yard=yard, tol=tol)
+
+
+def worst_ratio(got, ref, tol):
+    """max over the tensors of max |got - ref| / tolerance, and the list of the ratios"""
+    r = [float((g.double() - x.double()).abs().max()) / t if x.numel() else 0.0 for g, x, t in zip(got, ref, tol)]
+    return max(r), r
+
+
+# the cases of tests/test_gpu_attn_edges.py (tests/test_attn_laws_host.py checks the families' conditions on the same ones)
+ATTN_HEAD_DIMS = (32, 64)
+ATTN_M_EDGES = [(2, 65, M, 2) for M in (1, 15, 16, 17, 31, 32, 33, 47, 48, 63, 64)]           # the 16-key tile edges
+ATTN_N_EDGES = [(1, N, 49, 1) for N in (1, 63, 64, 65, 255, 256, 257, 511, 512, 513, 639, 640, 641)] + [(2, 513, 49, 5)]
+ATTN_KEYS_EDGES = [(1, 65, 65, 1), (1, 513, 129, 1), (1, 641, 200, 1), (1, 64, 256, 1), (1, 130, 255, 1)]
+ATTN_SCALE_CASES = [(2, 65, 33, 2, 0.3), (2, 65, 33, 2, 0.0)]                                  # unit family, scale != d^-0.5 and scale = 0
+# (B, H, W, w, s, heads): 6, 3, 5, 8, 4, 2, 3 and 18 workgroups per head; the first and the last shift; every window size
+WINDOW_EDGES = [(1, 8, 12, 4, 1, 2), (1, 4, 12, 4, 3, 1), (5, 7, 7, 7, 6, 1), (2, 6, 6, 3, 1, 2), (1, 10, 10, 5, 2, 1), (1, 12, 6, 6, 5, 1),
+                (3, 2, 2, 2, 1, 1), (2, 3, 3, 1, 0, 2)]
+WINDOW_HOT = [(1, 14, 14, 7, 3, 1, 32), (1, 8, 12, 4, 1, 1, 32), (1, 8, 8, 4, 3, 1, 64), (1, 16, 16, 8, 7, 1, 32)]      # (.., d): where `hot` was sized

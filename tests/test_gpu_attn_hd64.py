@@ -9,7 +9,7 @@ import torch
 from hpfg_amd import _lib as L
 from hpfg_amd import ops_tokens
 from hpfg_amd.ops_tokens import attention
-from tests.helpers import maxerr
+from tests.helpers import ATTN_YARDSTICK, attn_f64, attn_tolerance, maxerr, worst_ratio
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -52,6 +52,12 @@ def test_attention_core_head_dim_64(B, N, M, heads, math):
     assert e_out < b_out
     assert e_dq < b_dq
     assert e_dkv < b_dkv
+    # and against the float64 law under the rule of tests/test_gpu_attn_edges.py: 8 x the error of the mode's yardstick against the law
+    law = attn_f64(q, kv, do, heads, d, scale)
+    tol = attn_tolerance(law, attn_f64(q, kv, do, heads, d, scale, arith=ATTN_YARDSTICK[math]))
+    _, ratios = worst_ratio((out.detach().cpu(), qd.grad.cpu(), kd.grad.cpu()), (law[0], law[2], law[3]), (tol[0], tol[2], tol[3]))
+    print(f"hd64 {math} B={B} N={N} M={M} heads={heads}: out {ratios[0]:.3f}  dq {ratios[1]:.3f}  dkv {ratios[2]:.3f}   (error / tolerance against float64)")
+    assert max(ratios) < 1.0
 
 
 @pytest.mark.parametrize("B,N,M,heads", [(2, 3136, 49, 1), (3, 1100, 33, 5), (1, 10, 64, 2)])

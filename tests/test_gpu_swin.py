@@ -19,6 +19,9 @@ from hpfg_amd import ops_tokens
 from hpfg_amd.model import BasicBlock, SwinTransformerBlock
 from hpfg_amd.ops_tokens import attention, gelu, patch_merge, window_attention
 from tests.helpers import maxerr
+from tests.helpers import window_attn_reference as _reference
+from tests.helpers import window_partition as _partition
+from tests.helpers import window_reverse as _reverse
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -27,49 +30,6 @@ MATH = {"f32": 0, "bf16x3": 1}
 # (B, H = W, w, s, heads, d): four windows; all nine mask regions meet inside windows; window == map (wrap-around only); 16 keys (the
 # padded-key path); exactly 64 keys (no padding)
 SHAPES = [(2, 14, 7, 0, 2, 32), (2, 14, 7, 3, 2, 32), (1, 7, 7, 3, 1, 64), (1, 8, 4, 2, 3, 32), (1, 16, 8, 4, 1, 32)]
-
-
-def _partition(x, w):
-    """[B,H,W,...] -> [B * nW, w * w, ...] (window_partition of the reference)"""
-    B, H, W = x.shape[:3]
-    rest = x.shape[3:]
-    k = len(rest)
-    return x.reshape(B, H // w, w, W // w, w, *rest).permute(0, 1, 3, 2, 4, *range(5, 5 + k)).reshape(B * (H // w) * (W // w), w * w, *rest)
-
-
-def _reverse(xw, B, H, W, w):
-    C_ = xw.shape[-1]
-    return xw.reshape(B, H // w, W // w, w, w, C_).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C_)
-
-
-def _reference(qkv, table, heads, w, s, scale):
-    """WindowAttention.forward of the reference between its qkv and proj Linear, written out"""
-    B, H, W, C3 = qkv.shape
-    C_, L_ = C3 // 3, w * w
-    d = C_ // heads
-    x = torch.roll(qkv, (-s, -s), (1, 2)) if s else qkv
-    xw = _partition(x, w).reshape(-1, L_, 3, heads, d).permute(2, 0, 3, 1, 4)            # [3, Bn, heads, L, d]
-    q, k, v = xw[0] * scale, xw[1], xw[2]
-    a = q @ k.transpose(-2, -1)
-    l = torch.arange(L_)
-    i, j = l // w, l % w
-    idx = (i[:, None] - i[None, :] + w - 1) * (2 * w - 1) + (j[:, None] - j[None, :] + w - 1)
-    a = a + table[idx.reshape(-1)].reshape(L_, L_, heads).permute(2, 0, 1)[None]
-    if s:
-        img = torch.zeros(1, H, W, 1, dtype=qkv.dtype)
-        cnt = 0
-        for hs in (slice(0, -w), slice(-w, -s), slice(-s, None)):
-            for ws in (slice(0, -w), slice(-w, -s), slice(-s, None)):
-                img[:, hs, ws, :] = cnt
-                cnt += 1
-        mw = _partition(img, w).reshape(-1, L_)
-        m = mw[:, None, :] - mw[:, :, None]
-        m = torch.where(m != 0, torch.full_like(m, -100.0), torch.zeros_like(m))
-        nW = m.shape[0]
-        a = (a.reshape(B, nW, heads, L_, L_) + m[None, :, None]).reshape(-1, heads, L_, L_)
-    o = (a.softmax(-1) @ v).transpose(1, 2).reshape(-1, L_, C_)
-    o = _reverse(o, B, H, W, w)
-    return torch.roll(o, (s, s), (1, 2)) if s else o
 
 
 @functools.lru_cache(maxsize=None)

@@ -4,7 +4,7 @@ import torch
 import torch.nn.functional as F
 
 from hpfg_amd.ops_tokens import attention, bn_relu_dropout, dwconv_gelu, im2col, layer_norm, linear, residual_scale, resize_bilinear
-from tests.helpers import maxerr
+from tests.helpers import ATTN_YARDSTICK, attn_f64, attn_tolerance, maxerr, worst_ratio
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -31,7 +31,8 @@ def test_layer_norm(rows, C_):
                                          (2, 3136, 49, 1), (1, 784, 49, 2), (3, 1100, 33, 5)])
 def test_attention_core(B, N, M, heads, math):
     """softmax(scale q k^T) v and its three gradients: the MFMA kernels (csrc/attn.hip, split-bf16 products: default math mode) and the exact-fp32
-    thread-per-query kernels (HPFG_MATH=f32) against plain PyTorch fp32."""
+    thread-per-query kernels (HPFG_MATH=f32) against plain PyTorch fp32 at the hand bounds below, and against the float64 law under the rule
+    of tests/test_gpu_attn_edges.py (8 x the error of the mode's yardstick against the law)."""
     from hpfg_amd import ops_tokens
     g = torch.Generator().manual_seed(N + M)
     C_ = heads * 32
@@ -56,6 +57,11 @@ def test_attention_core(B, N, M, heads, math):
     assert maxerr(out.detach().cpu(), ref(q, kv)) < 2e-5 * k
     assert maxerr(qd.grad.cpu(), qr.grad) < 5e-5 * k
     assert maxerr(kd.grad.cpu(), kr.grad) < 2e-4 * k * max(1.0, (N / 256) ** 0.5)        # dK / dV sum over all N queries
+    law = attn_f64(q, kv, do, heads, 32, scale)
+    tol = attn_tolerance(law, attn_f64(q, kv, do, heads, 32, scale, arith=ATTN_YARDSTICK[math]))
+    _, ratios = worst_ratio((out.detach().cpu(), qd.grad.cpu(), kd.grad.cpu()), (law[0], law[2], law[3]), (tol[0], tol[2], tol[3]))
+    print(f"attention core {math} B={B} N={N} M={M} heads={heads}: out {ratios[0]:.3f}  dq {ratios[1]:.3f}  dkv {ratios[2]:.3f}   (error / tolerance)")
+    assert max(ratios) < 1.0
 
 
 @pytest.mark.parametrize("B,H,W,C_", [(2, 16, 16, 128), (2, 8, 8, 256), (1, 4, 4, 640), (2, 2, 2, 1024), (1, 7, 5, 128)])
