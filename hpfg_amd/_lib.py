@@ -19,7 +19,7 @@ OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP, OPT_UPDATE_PACK
 LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
 LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 142
+VERSION = 143
 RESIZE_TAPS = 36            # HPFG_RESIZE_TAPS: coefficients per output sample and axis of hpfg_resize_cubic's tap tables
 SURFACE_SEGS = 32           # HPFG_SURFACE_SEGS: surface-point segments of hpfg_surface_*, (class - 1) * 2 + side (0 = pred, 1 = gt)
 MATH_F32, MATH_BF16X3 = 0, 1
@@ -245,6 +245,12 @@ PROTOTYPES = {
     "hpfg_patch_merge_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "hpfg_attn_fwd_hd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "hpfg_attn_bwd_hd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "hpfg_mae_window_mask": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "hpfg_mae_mask_tokens_fwd": (_i, [_p, _p, _p, _p, _l, _i, _p]),
+    "hpfg_mae_mask_tokens_bwd": (_i, [_p, _p, _p, _p, _p, _l, _i, _p]),
+    "hpfg_mae_mask_tokens_bwd_blocks": (_i, [_l]),
+    "hpfg_mae_loss": (_i, [_p, _p, _p, _f, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "hpfg_mae_loss_blocks": (_l, [_i, _i, _i, _i]),
     "hpfg_gemm_f32": (_i, [_p, _l, _l, _p, _l, _l, _p, _l, _i, _i, _i, _p, _i, _i, _p]),
     "hpfg_gemm_f32_splitk": (_i, [_p, _l, _l, _p, _l, _l, _p, _l, _i, _i, _i, _p, _i, _i, _p, _p]),
     "hpfg_gemm_f32_splits": (_i, [_i, _i, _i]),

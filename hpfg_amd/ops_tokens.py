@@ -1,5 +1,5 @@
 """Autograd bindings of the token-layout HIP kernels (csrc/tokens.hip) used by the SegFormer branch: LayerNorm, the attention core
-softmax(q k^T) v, depthwise-3x3 + GELU, and the shifted-window attention, GELU and patch merging of the Swin blocks (csrc/attn_window.hip).  Device tensors only; the library raises if it is missing (no fallback)."""
+softmax(q k^T) v, depthwise-3x3 + GELU, and the shifted-window attention, GELU and patch merging of the Swin blocks (csrc/attn_window.hip), and the window mask, mask-token substitution and masked loss of the Swin-MAE pretraining (csrc/mae.hip).  Device tensors only; the library raises if it is missing (no fallback)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -775,3 +775,121 @@ class _ResidualScale(torch.autograd.Function):
 def residual_scale(x: torch.Tensor, y: torch.Tensor, scale=None) -> torch.Tensor:
     """x + y * scale[b] per sample b (scale None = 1): a residual branch with stochastic depth in one kernel."""
     return _ResidualScale.apply(x, y, scale)
+
+
+# ---- Swin-MAE pretraining (csrc/mae.hip) ------------------------------------------------------------------------------------------------------
+MAE_MAX_GROUPS, MAE_MAX_C, MAE_PATCH, MAE_MAX_CIN = 1024, 1536, 4, 4          # what hpfg_mae_window_mask / _mask_tokens_* / _loss are built for
+
+
+def mae_keep_count(d: int, mask_ratio: float) -> int:
+    """Groups the window masking keeps out of d * d: the reference's own expression in Python floats, truncation included
+    (model/swin_mae.py:673; 0.6 at d = 14 gives 78)."""
+    return int(d ** 2 * (1 - mask_ratio))
+
+
+def _mask_args(who, mask, n):
+    if mask.dtype != torch.uint8 or mask.numel() != n:
+        raise ValueError(f"{who}: mask must be uint8 with {n} elements (one per token), got {mask.dtype} {tuple(mask.shape)}")
+
+
+def mae_window_mask(noise: torch.Tensor, side: int, r: int, n_keep: int) -> torch.Tensor:
+    """window_masking(remove=False, mask_len_sparse=False) of the reference's SwinMAE from its noise: noise [B, d * d] (d = side / r) ->
+    uint8 mask [B, side * side] in token order y * side + x, 1 = removed; the n_keep groups of r x r tokens with the smallest (noise, index)
+    are kept.  No host round trip (the reference's np.setdiff1d loop), so the call can be captured."""
+    if side < 1 or r < 1 or side % r:
+        raise ValueError(f"mae_window_mask: the token side {side} must be a positive multiple of the group side r = {r}")
+    d = side // r
+    if d * d > MAE_MAX_GROUPS:
+        raise ValueError(f"mae_window_mask: {d} x {d} groups; the kernel ranks at most {MAE_MAX_GROUPS} per image")
+    if noise.dim() != 2 or noise.shape[1] != d * d or noise.shape[0] < 1:
+        raise ValueError(f"mae_window_mask: noise {tuple(noise.shape)} must be [B, d * d = {d * d}]")
+    if not 0 <= n_keep <= d * d:
+        raise ValueError(f"mae_window_mask: n_keep = {n_keep} must be in 0 .. {d * d}")
+    _need_gpu(noise, "mae_window_mask")
+    nc = noise.contiguous().float()
+    mask = torch.empty(nc.shape[0], side * side, dtype=torch.uint8, device=noise.device)
+    L.check(L.load().hpfg_mae_window_mask(L.ptr(nc), L.ptr(mask), nc.shape[0], int(side), int(r), int(n_keep), _st(noise)), "mae_window_mask")
+    return mask
+
+
+class _MaeMaskTokens(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, token):
+        xc, tc = x.contiguous().float(), token.contiguous().float().reshape(-1)
+        C_ = xc.shape[-1]
+        rows = xc.numel() // C_
+        y = torch.empty_like(xc)
+        L.check(L.load().hpfg_mae_mask_tokens_fwd(L.ptr(xc), L.ptr(mask), L.ptr(tc), L.ptr(y), rows, C_, _st(x)), "mae_mask_tokens_fwd")
+        ctx.mask, ctx.geo = mask, (rows, C_, token.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.load()
+        rows, C_, tshape = ctx.geo
+        dyc = dy.contiguous()
+        dx = torch.empty_like(dyc)
+        dtok = torch.empty(C_, dtype=torch.float32, device=dy.device)
+        part = torch.empty(lib.hpfg_mae_mask_tokens_bwd_blocks(rows) * C_, dtype=torch.float32, device=dy.device)
+        L.check(lib.hpfg_mae_mask_tokens_bwd(L.ptr(dyc), L.ptr(ctx.mask), L.ptr(dx), L.ptr(dtok), L.ptr(part), rows, C_, _st(dy)), "mae_mask_tokens_bwd")
+        return dx, None, dtok.view(tshape)
+
+
+def mae_mask_tokens(x: torch.Tensor, mask: torch.Tensor, token: torch.Tensor) -> torch.Tensor:
+    """x [.., C] with every token whose mask byte is non-zero replaced by ``token`` (C values; the reference's per-image
+    ``x_masked[i, index_mask[i], :] = self.mask_token``, model/swin_mae.py:706-709).  Gradients: dx = dy on kept tokens, 0 on masked ones;
+    dtoken = the sum of dy over the masked tokens (fixed order).  C % 4 == 0, 4 <= C <= MAE_MAX_C; mask uint8, one byte per token."""
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"mae_mask_tokens: x {tuple(x.shape)} must be a non-empty [.., tokens, C]")
+    C_ = x.shape[-1]
+    if C_ % 4 or not 4 <= C_ <= MAE_MAX_C:
+        raise ValueError(f"mae_mask_tokens: C = {C_} is not built; the kernels take C % 4 == 0, 4 <= C <= {MAE_MAX_C}")
+    if token.numel() != C_:
+        raise ValueError(f"mae_mask_tokens: the mask token must have C = {C_} elements, got {tuple(token.shape)}")
+    _mask_args("mae_mask_tokens", mask, x.numel() // C_)
+    _need_gpu(x, "mae_mask_tokens")
+    if not mask.is_cuda:
+        raise ValueError("mae_mask_tokens: mask must be on the device")
+    return _MaeMaskTokens.apply(x, mask.contiguous(), token)
+
+
+class _MaeLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, img, mask, scale, norm_pix):
+        lib = L.load()
+        pc, ic = pred.contiguous().float(), img.contiguous().float()
+        B, Cin, H, W = ic.shape
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        dpred = torch.empty_like(pc)
+        part = torch.empty(lib.hpfg_mae_loss_blocks(B, H, W, MAE_PATCH), dtype=torch.float32, device=pred.device)
+        L.check(lib.hpfg_mae_loss(L.ptr(pc), L.ptr(ic), L.ptr(mask), scale, 1 if norm_pix else 0, L.ptr(loss), L.ptr(dpred), L.ptr(part), B, Cin, H, W,
+                                  MAE_PATCH, _st(pred)), "mae_loss")
+        ctx.dpred = dpred          # the gradient for an upstream gradient of 1, written by the forward launch
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dpred = ctx.dpred
+        out = torch.empty_like(dpred)
+        L.check(L.load().hpfg_scale_rows(L.ptr(dpred), L.ptr(dloss.contiguous().float().reshape(1)), L.ptr(out), 1, dpred.numel(), _st(dpred)),
+                "mae_loss (backward)")
+        return out, None, None, None, None
+
+
+def mae_loss(pred: torch.Tensor, img: torch.Tensor, mask: torch.Tensor, scale: float, norm_pix: bool = False) -> torch.Tensor:
+    """scale * sum over masked tokens of sum_j (pred - patchify(img))^2 as a 0-dim device tensor (no host synchronisation), its gradient to
+    ``pred`` saved from the same launch.  pred [B, L, 16 Cin] as ``decoder_pred`` writes it (channel order (p, q, c)), img [B, Cin, H, W] read
+    in place through the patchify addressing, mask uint8 [B, L] (non-zero = removed).  scale = 1 / (B Cin H W mask_ratio) is the driver's
+    ``mean((pred_img - img)^2 mask_img) / mask_ratio`` (2022_12_CVPR_Swin-MAE.py:112), scale = 1 / (16 Cin n_masked) the model's
+    ``forward_loss`` (model/swin_mae.py:775-791), whose per-patch target normalisation ``norm_pix`` switches on.  Patch 4, 1 <= Cin <= 4."""
+    if img.dim() != 4 or not 1 <= img.shape[1] <= MAE_MAX_CIN or img.shape[2] % MAE_PATCH or img.shape[3] % MAE_PATCH or img.numel() == 0:
+        raise ValueError(f"mae_loss: img {tuple(img.shape)} must be [B, 1 <= Cin <= {MAE_MAX_CIN}, H, W] with sides divisible by the patch {MAE_PATCH}")
+    B, Cin, H, W = img.shape
+    Ltok, D = (H // MAE_PATCH) * (W // MAE_PATCH), MAE_PATCH * MAE_PATCH * Cin
+    if tuple(pred.shape) != (B, Ltok, D):
+        raise ValueError(f"mae_loss: pred {tuple(pred.shape)} must be [B, L, patch^2 Cin] = [{B}, {Ltok}, {D}] for img {tuple(img.shape)}")
+    _mask_args("mae_loss", mask, B * Ltok)
+    _need_gpu(pred, "mae_loss")
+    if not (mask.is_cuda and img.is_cuda):
+        raise ValueError("mae_loss: img and mask must be on the device")
+    return _MaeLoss.apply(pred, img, mask.contiguous(), float(scale), bool(norm_pix))

@@ -4,6 +4,7 @@
   MeanTeacherStep   2017_03_NIPS_Mean-Teacher_ACDC.py:82-113   (Mean_Teacher)
   CPSStep           2021_06_CVPR_CPS_ACDC.py:83-120            (CPS)
   HPFGStep          main.py:125-212              (HPFG, incl. update_ema_variables_backbone main.py:68-76)
+  SwinMAEStep       2022_12_CVPR_Swin-MAE.py:105-117             (Swin_MAE)
   ICTStep / UAMTStep / CTCTStep / S4CVNetStep   the loop bodies of 2022_02_ISBI_ICT-MedSeg_ACDC.py, 2019_07_MICCAI_Uncertainty_Aware_ACDC.py,
                     2021_12_MIDL_CTCT_ACDC.py (CTCT) and 2022_08_CVPR_S4CVNet_ACDC.py on the same kernels
 
@@ -319,6 +320,33 @@ class SupervisedStep(_StepBase):
 
     def step(self, img, label, cur_itrs):
         return self.eager_step((img, label), cur_itrs)
+
+
+class SwinMAEStep(_StepBase):
+    """Masked-autoencoder pretraining of the Swin encoder (2022_12_CVPR_Swin-MAE.py:105-117): one forward of the SwinMAE network -- the
+    reference calls the model twice by mistake and keeps the second call; it runs once here --, the driver's loss
+    ``mean((pred_img - img)^2 * mask_img) / mask_ratio`` from ``mae_loss`` without either image, backward, and the update.  The window mask is
+    drawn, applied and consumed on the device (csrc/mae.hip), so the step has no host round trip and ``GraphedStep`` captures it whole; every
+    replay draws a new mask (torch's device generator).  The optimizer and scheduler come from ``build_optimizer`` / ``build_lr_scheduler``
+    (the reference uses timm's factories: its no-weight-decay group for 1-D parameters is not reproduced).  The frozen ``pos_embed`` lies
+    behind the trainable parameters in the flat buffer and is neither stepped nor decayed."""
+
+    def __init__(self, model, args, dp=None):
+        if dp is not None:
+            raise NotImplementedError("SwinMAEStep: data parallel (dp is not None) is not built for this step")
+        super().__init__(args, dp, [model])
+
+    def host_scalars(self, cur_itrs):
+        self.sc.host[S_LR1] = self._lr(self.optimizer)
+
+    def device_fwd_bwd(self, img):
+        loss, pred, mask = self.model.reconstruction_loss(img, with_parts=True)
+        self.optimizer.zero_grad()
+        loss.backward()
+        return {"loss": loss.detach(), "pred": pred.detach(), "mask": mask}
+
+    def step(self, img, cur_itrs):
+        return self.eager_step((img,), cur_itrs)
 
 
 class _TeacherStudentStep(_StepBase):
@@ -1112,6 +1140,29 @@ def Supervise(model, train_loader, test_loader, args):
     emit = lambda row, h: {"supervise/loss": row[0], "supervise/lr": h["lr"]}
     run = _LoopRunner(st, args, 8, emit, ["parts"], lambda: {"lr": st._lr(st.optimizer)})
     return run.drive(train_loader, list, test_loader, [(best, model, st.optimizer, st.lr_scheduler, "test")])      # batch = (img, label_true)
+
+
+def Swin_MAE(model, train_loader, test_loader, args):
+    """2022_12_CVPR_Swin-MAE.py:79-164 (its ``Supervise``): ``supervise/loss`` and ``supervise/lr`` per iteration, and the reference's
+    checkpoint {"model", "optimizer"} at ``args.supervise_save_path`` (or save_path/model/supervise_model.pth) every ``step_size`` iterations
+    -- the cadence of the other loops here; the reference writes it once per epoch.  Nothing is evaluated (pretraining has no metric; the
+    reference's TensorBoard image grids are not produced), so ``test_loader`` is not read."""
+    st = SwinMAEStep(model, args, getattr(args, "dp", None))
+    model.train()
+
+    def save(model, optimizer, lr_scheduler, test_loader, cur_itrs, name):
+        path = getattr(args, "supervise_save_path", None)
+        if not path and getattr(args, "save_path", None):
+            path = os.path.join(args.save_path, "model", "supervise_model.pth")
+        if path:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            torch.save({"cur_itrs": cur_itrs, "model": model.state_dict(), "optimizer": optimizer.state_dict()}, path)
+
+    emit = lambda row, h: {"supervise/loss": row[0], "supervise/lr": h["lr"]}
+    run = _LoopRunner(st, args, 1, emit, ["loss"], lambda: {"lr": st._lr(st.optimizer)})
+    # batch = (img, label_true): the labels are not used.  (a loop without a test loader still saves: drive only asks whether there is one)
+    return run.drive(train_loader, lambda batch: [batch[0]], test_loader if test_loader is not None else (),
+                     [(save, model, st.optimizer, st.lr_scheduler, "test")])
 
 
 def Mean_Teacher(model, ema_model, label_loader, unlabel_loader, test_loader, args):

@@ -149,13 +149,22 @@ class FusedSGD(torch.optim.Optimizer):
             self._mom.copy_(mom)
 
 
+def flat_order(model):
+    """The order in which ``flatten_parameters`` lays a module's parameters into its flat buffer: ``parameters()`` order with the frozen ones
+    (requires_grad False) moved behind the trainable ones when a module has both -- a frozen parameter gets no gradient and must not be
+    stepped or decayed, and the flat kernels can only leave out a trailing range (``active_numel``).  A module whose parameters are all
+    trainable, or all frozen (an EMA teacher), keeps ``parameters()`` order.  Swin-MAE's ``pos_embed`` is the one mixed case."""
+    ps = list(model.parameters())
+    return [p for p in ps if p.requires_grad] + [p for p in ps if not p.requires_grad]
+
+
 def flatten_parameters(model):
     """Re-point every parameter of `model` at a slice of ONE flat fp32 buffer (gradients are packed into a second flat buffer per step), so
     that an optimizer step is a single kernel.  The hpfg_amd U-Nets are built that way; this does it for any module (SegFormer).
     Must run after the module is on its device.  Sets model.flat_params / model.flat_grads."""
     if hasattr(model, "flat_params"):
         return
-    ps = [p for p in model.parameters()]
+    ps = flat_order(model)
     dev = ps[0].device
     n = sum(p.numel() for p in ps)
     flat = torch.empty(n, dtype=torch.float32, device=dev)
@@ -168,6 +177,7 @@ def flatten_parameters(model):
             p.data = flat[o:o + k].view(p.shape)
             o += k
     model.flat_params, model.flat_grads = flat, grad
+    model._hpfg_flat_order = ps          # the layout, whatever happens to requires_grad afterwards (gather_flat_grads packs in this order)
     model._hpfg_generic_flat = True      # gradients reach flat_grads only through FusedAdamW.gather_flat_grads()
 
 
@@ -184,7 +194,7 @@ def gather_flat_grads(model, active_numel=None):
     BasicBlock's ``downsample`` only where it is applied; a dropped path yields a zero gradient, not a missing one), and the one trailing
     group a step leaves out -- the necks of HPFG's first student -- is cut off by active_numel.  Anything else is refused."""
     ps, k = [], 0
-    for p in model.parameters():
+    for p in getattr(model, "_hpfg_flat_order", None) or list(model.parameters()):
         if active_numel is not None and k >= active_numel:
             break
         ps.append(p)
@@ -192,7 +202,8 @@ def gather_flat_grads(model, active_numel=None):
     assert active_numel is None or k == active_numel, "active_numel must end on a parameter boundary"
     missing = [i for i, p in enumerate(ps) if p.grad is None]
     if missing:
-        names = [n for i, (n, _) in enumerate(model.named_parameters()) if i in set(missing)]
+        ids = {id(ps[i]) for i in missing}
+        names = [n for n, p in model.named_parameters() if id(p) in ids]
         raise RuntimeError(f"gather_flat_grads: {len(missing)} parameter(s) inside the updated range have no gradient ({', '.join(names[:4])}"
                            f"{', ...' if len(names) > 4 else ''}): torch's optimizers would skip them, the flat kernels would decay them. "
                            "Lay parameters that a step leaves out at the end of the module and set the optimizer's active_numel")
@@ -225,6 +236,9 @@ class FusedAdamW(torch.optim.Optimizer):
         # torch.optim.AdamW skips a parameter whose .grad is None: no moment update, no step, and no weight decay either.  A step that never
         # back-propagates into a trailing part of the flat buffer (HPFG's first student: its necks) says so here, as on FusedSGD.
         self.active_numel = None
+        n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
+        if 0 < n_train < flat.numel():          # frozen parameters lie behind the trainable ones (flat_order): the update stops in front of them
+            self.active_numel = n_train
         model._hpfg_flat_optimizer = self
 
     def zero_grad(self, set_to_none: bool = True):

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 142
+#define HPFG_VERSION 143
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -659,6 +659,35 @@ int hpfg_attn_window_drop_bwd(const float* qkv, const float* bias_table, const f
                               const uint8_t* mask, void* stream);
 long hpfg_attn_window_drop_elems(int B, int H, int W, int heads, int window);
 int hpfg_attn_window_drop_mask(uint8_t* out, int B, int H, int W, int heads, int window, float p, uint32_t seed, const uint32_t* seed_dev, void* stream);
+
+/* ---- Swin-MAE pretraining (csrc/mae.hip; reference model/swin_mae.py, 2022_12_CVPR_Swin-MAE.py) ------------------------------------------ */
+/* window_masking with remove=False, mask_len_sparse=False (reference model/swin_mae.py:649-710) from a given noise tensor: the S x S token map
+ * is cut into d x d groups of r x r tokens (d = S / r); a group is kept iff its rank among the image's d * d noise values, ascending by
+ * (noise, index) -- torch.argsort made total --, is below n_keep; mask [B, S * S] uint8 in token order y * S + x, 1 = removed.  One workgroup
+ * per image ranks by counting against the noise row in LDS: d * d <= 1024.  n_keep = int(d * d * (1 - mask_ratio)) is the caller's (:673).
+ * Returns -1 and sets hpfg_last_error on a null pointer, S % r != 0, more than 1024 groups or n_keep outside 0 .. d * d. */
+int hpfg_mae_window_mask(const float* noise, uint8_t* mask, int B, int S, int r, int n_keep, void* stream);
+/* x_masked[i, index_mask[i], :] = mask_token (reference model/swin_mae.py:706-709) over rows = B * L tokens of C channels:
+ * y[row, :] = mask[row] ? token : x[row, :]; a masked row of x is not read.  C % 4 == 0, 4 <= C <= 1536. */
+int hpfg_mae_mask_tokens_fwd(const float* x, const uint8_t* mask, const float* token, float* y, long rows, int C, void* stream);
+/* its backward (reference model/swin_mae.py:706-709 under autograd): dx = dy on kept rows and 0 on masked ones; dtoken[c] = sum of dy[row, c]
+ * over the masked rows -- per-workgroup partial sums over contiguous row ranges, then one finishing kernel that adds them in a fixed order
+ * (no atomics: equal bits from run to run).  partials: hpfg_mae_mask_tokens_bwd_blocks(rows) * C floats of scratch. */
+int hpfg_mae_mask_tokens_bwd(const float* dy, const uint8_t* mask, float* dx, float* dtoken, float* partials, long rows, int C, void* stream);
+int hpfg_mae_mask_tokens_bwd_blocks(long rows);
+/* The masked reconstruction loss and its gradient from one pass over pred (reference model/swin_mae.py:775-791 forward_loss and
+ * 2022_12_CVPR_Swin-MAE.py:112): pred [B, L, patch^2 Cin] with the channel order (p, q, c) of decoder_pred, img [B, Cin, H, W] read through
+ * the patchify addressing (:621-633: target[b, h Wp + w, (p patch + q) Cin + c] = img[b, c, h patch + p, w patch + q]) -- no patchified or
+ * un-patchified copy is made --, mask [B, L] (non-zero = removed).  *loss = scale * sum over masked tokens of sum_j (pred - target)^2;
+ * dpred = 2 scale (pred - target) on masked tokens, 0 on kept ones, whose pred rows and pixels are not read.  norm_pix != 0: the target patch is
+ * normalised first, (t - mean) / sqrt(var + 1e-6) with the unbiased variance over its patch^2 Cin values (:782-785).  scale = 1 / (B Cin H W
+ * mask_ratio) gives the driver's mean((pred_img - img)^2 mask_img) / mask_ratio, scale = 1 / (patch^2 Cin n_masked) forward_loss.
+ * Two kernels on the stream, no host synchronisation: token sums -> one partial per workgroup (fixed tree), then one workgroup adds the
+ * partials in index order and writes *loss (device).  partials: hpfg_mae_loss_blocks(B, H, W, patch) floats (-1 for a shape that is refused).
+ * patch == 4, 1 <= Cin <= 4, H % 4 == 0, W % 4 == 0. */
+int hpfg_mae_loss(const float* pred, const float* img, const uint8_t* mask, float scale, int norm_pix, float* loss, float* dpred, float* partials,
+                  int B, int Cin, int H, int W, int patch, void* stream);
+long hpfg_mae_loss_blocks(int B, int H, int W, int patch);
 
 /* ---- projection necks + Dense_Loss (UNet_Plus; reference model/unet.py:120-152, utils/loss/dense_loss.py:17-40) ------------------------ */
 /* C[m,n] = act(sum_k A(m,k) B(k,n) + bias[n]) in exact fp32 on the matrix cores; A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn], C row-major
