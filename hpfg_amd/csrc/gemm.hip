@@ -2,7 +2,8 @@
 // MFMA"), with arbitrary element strides on both operands so that one kernel serves  Y = X W^T + b (ReLU) ,  dX = dY W ,  dW = dY^T X
 // of the projection necks (reference model/unet.py:125-138: Linear / 1x1 conv stacks) and the Gram matrices of Dense_Loss
 // (utils/loss/dense_loss.py:24).  These products are a few hundred MFLOP per step: what matters is that they are ours (no rocBLAS /
-// MIOpen on the path), exact, deterministic (no split-K, no atomics) and capturable.
+// MIOpen on the path), exact, deterministic (no atomics; where the contraction is split over workgroups, hpfg_gemm_f32_splitk, the partial
+// products are added in split order by one finishing launch) and capturable.
 //
 //   C[m, n] = act( sum_k A(m, k) * B(k, n) + bias[n] ),   A(m, k) = A[m*sam + k*sak],   B(k, n) = B[k*sbk + n*sbn],   C row-major (ldc)
 //
@@ -137,12 +138,18 @@ inline int f32_splits(int M, int N, int K) {
   return (int)(s < 1 ? 1 : (s > 32 ? 32 : s));
 }
 
-// out[c] = sum_r x[r, c]  (bias gradients of the neck layers): one thread per column, rows in a fixed order
+// out[c] = sum_r x[r, c]  (bias gradients of the neck layers): one thread per column, rows in a fixed order.  The sum is compensated
+// (Kahan): a plain running sum loses R / 2 ulp of the total, which at R = 2049 was 1.6 x the 8 x-torch bound of the float64 tests.
 __global__ void col_sum_kernel(const float* x, long R, int M, long ldx, float* out) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= M) return;
-  float s = 0.f;
-  for (long r = 0; r < R; ++r) s += x[r * ldx + c];
+  float s = 0.f, lost = 0.f;
+  for (long r = 0; r < R; ++r) {
+    const float y = x[r * ldx + c] - lost;
+    const float t = s + y;
+    lost = (t - s) - y;
+    s = t;
+  }
   out[c] = s;
 }
 

@@ -692,7 +692,8 @@ long hpfg_mae_loss_blocks(int B, int H, int W, int patch);
 /* ---- projection necks + Dense_Loss (UNet_Plus; reference model/unet.py:120-152, utils/loss/dense_loss.py:17-40) ------------------------ */
 /* C[m,n] = act(sum_k A(m,k) B(k,n) + bias[n]) in exact fp32 on the matrix cores; A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn], C row-major
  * (ldc); relu: max(.,0) in the epilogue; accumulate: C += (before the activation).  Replaces nn.Linear / 1x1 nn.Conv2d forward and both backward
- * products of the necks (unet.py:125-138) and torch.mm of dense_loss.py:24.  Deterministic: no split-K, no atomics. */
+ * products of the necks (unet.py:125-138) and torch.mm of dense_loss.py:24.  Deterministic: no atomics; this entry point does not split K, and
+ * hpfg_gemm_f32_splitk below adds its partial products in split order. */
 int hpfg_gemm_f32(const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc, int M, int N, int K,
                   const float* bias, int relu, int accumulate, void* stream);
 /* the same with the contraction split over workgroups when the product has few output tiles and a long K (fixed-order sum of the partials);

@@ -1391,3 +1391,440 @@ ATTN_SCALE_CASES = [(2, 65, 33, 2, 0.3), (2, 65, 33, 2, 0.0)]                   
 WINDOW_EDGES = [(1, 8, 12, 4, 1, 2), (1, 4, 12, 4, 3, 1), (5, 7, 7, 7, 6, 1), (2, 6, 6, 3, 1, 2), (1, 10, 10, 5, 2, 1), (1, 12, 6, 6, 5, 1),
                 (3, 2, 2, 2, 1, 1), (2, 3, 3, 1, 0, 2)]
 WINDOW_HOT = [(1, 14, 14, 7, 3, 1, 32), (1, 8, 12, 4, 1, 1, 32), (1, 8, 8, 4, 3, 1, 64), (1, 16, 16, 8, 7, 1, 32)]      # (.., d): where `hot` was sized
+
+
+# ---- float64 laws of the dense kernels (csrc/gemm.hip, csrc/heads.hip) --------------------------------------------------------------------
+# Plain restatements on double tensors: the product with its epilogue, column sums, adaptive average pooling, F.normalize and NT-Xent, each
+# with the named wrong variants its tolerance has to tell from rounding.  tests/test_dense_laws_host.py holds the laws against torch's own
+# float64 ops and autograd and shows every mutation caught; tests/test_gpu_gemm_edges.py and tests/test_gpu_heads_edges.py hold the kernels
+# against the laws.
+def ulp32(x):
+    """one unit in the last place of the float32 nearest to |x|"""
+    return float(np.spacing(np.float32(abs(float(x)))))
+
+
+def report(name, err, bound):
+    """One line per compared output: largest error / bound (pytest -s shows them; the GPU modules' docstrings quote a run)."""
+    ratio = err / bound if bound > 0 else (0.0 if err == 0 else float("inf"))
+    print(f"  {name:<60s} max|err| {err:9.3e}  bound {bound:9.3e}  ratio {ratio:6.3f}")
+    return ratio
+
+
+def within_bound(name, buf, ref64, bound):
+    """buf: canary_out(ref64.numel()) after the launch.  Every element written, the tail untouched, all finite, max |buf - ref64| <= bound.
+    -> the values as float64 in ref64's shape."""
+    n = ref64.numel()
+    written, tail = canary_ok(buf, n)
+    assert written, f"{name}: elements of the output were never written"
+    assert tail, f"{name}: the launch wrote past the end of the output"
+    got = buf[:n].cpu().double().reshape(ref64.shape)
+    assert bool(torch.isfinite(got).all()), f"{name}: not finite (a gap or canary element was read into the result)"
+    err = float((got - ref64.double()).abs().max())
+    report(name, err, bound)
+    assert err <= bound, (name, err, bound)
+    return got
+
+
+def nan_filled(n):
+    """n floats on the CPU, every one the NaN pattern of the canaries: the gaps of an operand with a leading dimension above its extent."""
+    return torch.full((n,), NAN_BITS, dtype=torch.int32).view(torch.float32)
+
+
+GEMM_MUTATIONS = ("lo_hi_dropped", "hi_hi_only", "last_k_dropped", "split_chunk_doubled", "bias_per_split", "relu_before_accumulate")
+TN_MUTATIONS = ("db_first_tile_only", "last_split_dropped")
+GEMM_TILE = {"f32": (64, 16, 32), "bf16x3": (128, 32, 16)}          # math -> (output tile edge, K chunk, largest split count)
+
+
+def gemm_split_geometry(math, M, N, K):
+    """(splits, kper, launched, k of the last launched split) of hpfg_gemm_{f32,bf16x3}_splitk, restated from the dispatch code: splits =
+    min(256 / tiles, K / 128, cap) unless there are 128 tiles or K < 256; kper = ceil(K / splits) rounded up to the K chunk; the launch
+    covers ceil(K / kper) slices, which can be fewer than `splits` (the scratch is still sized by `splits`)."""
+    T, chunk, cap = GEMM_TILE[math]
+    tiles = -(-M // T) * -(-N // T)
+    S = 1 if tiles >= 128 or K < 256 else max(1, min(256 // tiles, K // 128, cap))
+    if S <= 1:
+        return 1, K, 1, K
+    kper = -(-(-(-K // S)) // chunk) * chunk
+    launched = -(-K // kper)
+    return S, kper, launched, K - (launched - 1) * kper
+
+
+def tn_geometry(R, N, K):
+    """(splits, rows per split, rows of the last split) of hpfg_gemm_tn_bf16x3: 64 x 64 tiles over (N, K), splits = min(1024 / tiles,
+    ceil(R / 256), 512), rows per split rounded up to the 32 rows of a step."""
+    tiles = -(-N // 64) * -(-K // 64)
+    S = max(1, min(1024 // tiles, -(-R // 256), 512))
+    per = -(-(-(-R // S)) // 32) * 32
+    return S, per, R - (S - 1) * per
+
+
+def col_sum_geometry(R):
+    """(splits, rows per split) of hpfg_col_sum2"""
+    S = max(1, min(-(-R // 512), 256))
+    return S, -(-R // S)
+
+
+def _prod3_f64(a, b):
+    """_prod3 before its rounding: hi.hi + lo.hi + hi.lo in float64"""
+    ah, al = _bf16_split(a)
+    bh, bl = _bf16_split(b)
+    return ah @ bh + al @ bh + ah @ bl
+
+
+def gemm_f64(A, B, bias=None, C0=None, relu=False, mutation=None, kper=None, arith=torch.float64):
+    """The contract of include/hpfg_hip.h: act(A B + bias + C0), A [M,K], B [K,N], bias [N], C0 [M,N] (the accumulate switch), act = relu or
+    nothing.  arith: torch.float64 (the law), torch.float32 (torch's own float32 ops: the yardstick of the fp32 kernels) or "split" (the
+    three bf16 products of _prod3 summed without rounding, bias and C0 added in float64, one rounding to float32: the yardstick of the
+    split-bf16 kernels).  mutation: one of GEMM_MUTATIONS, evaluated in float64; the split ones take the split's `kper`."""
+    assert mutation is None or mutation in GEMM_MUTATIONS, mutation
+    if arith == torch.float32:
+        assert mutation is None
+        v = A.float() @ B.float()
+        if bias is not None:
+            v = v + bias.float()
+        if C0 is not None:
+            v = v + C0.float()
+        return torch.relu(v) if relu else v
+    A32, B32 = A.float(), B.float()
+    Ad, Bd = A32.double(), B32.double()
+    K = A.shape[1]
+    if arith == "split":
+        assert mutation is None
+        v = _prod3_f64(A32, B32)
+    elif mutation == "lo_hi_dropped":
+        (ah, al), (bh, bl) = _bf16_split(A32), _bf16_split(B32)
+        v = ah @ bh + ah @ bl
+    elif mutation == "hi_hi_only":
+        v = _bf16_split(A32)[0] @ _bf16_split(B32)[0]
+    elif mutation == "last_k_dropped":
+        v = Ad[:, :K - 1] @ Bd[:K - 1]
+    elif mutation == "split_chunk_doubled":
+        chunk = slice(kper, min(kper + 16, K))          # the first k-chunk of the second split
+        v = Ad @ Bd + Ad[:, chunk] @ Bd[chunk]
+    else:
+        v = Ad @ Bd
+    if bias is not None:
+        v = v + bias.double() * (-(-K // kper) if mutation == "bias_per_split" else 1)
+    if mutation == "relu_before_accumulate":
+        v = torch.relu(v) if relu else v
+        return v + C0.double() if C0 is not None else v
+    if C0 is not None:
+        v = v + C0.double()
+    v = torch.relu(v) if relu else v
+    return v.float() if arith == "split" else v
+
+
+def gemm_tolerance(math, law, y32, ysplit=None):
+    """fp32 kernels: bound_8x against torch's float32 result.  Split-bf16 kernels: that plus bound_8x against the split emulation -- the
+    second term covers the arithmetic the kernel is designed to make (hi.hi + lo.hi + hi.lo), the first its float32 accumulation over K."""
+    t = bound_8x(law, y32)
+    return t if math == "f32" else t + bound_8x(law, ysplit)
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_case(M, N, K, seed=0):
+    """Operands of one product on the CPU (float32; computed once, read-only): A [M,K] and Bt [N,K] through chan_affine's per-k scale and
+    offset (Bt times 0.2, as a weight), bias [N], C0 [M,N]; `law`, `y32`, `ysplit` and `tol` per math mode for the plain product without
+    epilogue; gemm_epilogue gives the same for an epilogue."""
+    g = torch.Generator().manual_seed(1000003 * M + 1009 * N + K + seed)
+    A, Bt = chan_affine((M, K), 0, g), 0.2 * chan_affine((N, K), 0, g)
+    bias, C0 = chan_affine((N,), 0, g), chan_affine((M, N), 0, g)
+    c = dict(M=M, N=N, K=K, A=A, Bt=Bt, B=Bt.t(), bias=bias, C0=C0)
+    c.update(gemm_epilogue(c, False, False, False))
+    return c
+
+
+def gemm_epilogue(c, bias, relu, acc):
+    """law, both yardsticks and the tolerance per math mode of act(A B (+ bias) (+ C0)) on a gemm_case"""
+    kw = dict(bias=c["bias"] if bias else None, C0=c["C0"] if acc else None, relu=bool(relu))
+    law = gemm_f64(c["A"], c["B"], **kw)
+    y32, ysplit = gemm_f64(c["A"], c["B"], arith=torch.float32, **kw), gemm_f64(c["A"], c["B"], arith="split", **kw)
+    return dict(law=law, y32=y32, ysplit=ysplit, tol={m: gemm_tolerance(m, law, y32, ysplit) for m in GEMM_TILE})
+
+
+def gemm_operand(vals, fast, pad):
+    """vals [rows, K] (A itself, or B transposed) laid out with the NaN pattern in every gap -> (flat float32 CPU buffer, srow, sk).
+    fast = "k": [rows][K + pad], (srow, sk) = (K + pad, 1).  fast = "r": [K][rows + pad], (1, rows + pad).  fast = "2": neither stride is
+    1, (2 K, 2) with the pattern at every odd index."""
+    rows, K = vals.shape
+    if fast == "k":
+        buf = nan_filled(rows * (K + pad)).view(rows, K + pad)
+        buf[:, :K] = vals
+        return buf.view(-1), K + pad, 1
+    if fast == "r":
+        buf = nan_filled(K * (rows + pad)).view(K, rows + pad)
+        buf[:, :rows] = vals.t()
+        return buf.view(-1), 1, rows + pad
+    assert fast == "2"
+    buf = nan_filled(rows * 2 * K).view(rows, K, 2)
+    buf[:, :, 0] = vals
+    return buf.view(-1), 2 * K, 2
+
+
+GEMM_ORIENTS = (("k", "k"), ("k", "r"), ("r", "k"), ("r", "r"))          # A k-fast / m-fast  x  B k-fast / n-fast
+GEMM_F32_SHAPES = ((1, 1, 1), (7, 5, 3), (64, 64, 16), (65, 63, 17), (63, 65, 15), (129, 1, 33))
+GEMM_BF16_SHAPES = ((4, 4, 4), (128, 128, 32), (132, 124, 36), (124, 132, 28), (260, 4, 68))
+GEMM_SCALAR_EPILOGUE = ((8, 7, 32, 7), (132, 37, 64, 37), (8, 8, 32, 11), (8, 8, 32, 16))          # (M, N, K, ldc): the last takes the vector epilogue
+GEMM_EPILOGUE_SHAPES = {"f32": ((65, 63, 17), (132, 124, 36)), "bf16x3": ((132, 124, 36),)}
+# (M, N, K) -> math -> (splits, kper, launched, k of the last split); None: the split-bf16 kernels do not take the shape
+GEMM_SPLIT_TABLE = {
+    (8, 8, 256): {"f32": (2, 128, 2, 128), "bf16x3": (2, 128, 2, 128)},
+    (5, 7, 257): {"f32": (2, 144, 2, 113), "bf16x3": None},
+    (8, 8, 264): {"f32": (2, 144, 2, 120), "bf16x3": (2, 160, 2, 104)},
+    (65, 63, 273): {"f32": (2, 144, 2, 129), "bf16x3": None},
+    (132, 68, 516): {"f32": (4, 144, 4, 84), "bf16x3": (4, 160, 4, 36)},
+    (8, 8, 2080): {"f32": (16, 144, 15, 64), "bf16x3": (16, 160, 13, 160)},
+}
+GEMM_UNSPLIT = (64, 64, 255)
+# (R, N, K, with_db) -> (splits, rows per split, rows of the last split)
+TN_CASES = {
+    (1, 4, 4, 1): (1, 32, 1), (31, 4, 8, 0): (1, 32, 31), (33, 36, 20, 1): (1, 64, 33), (300, 5, 7, 1): (2, 160, 140),
+    (257, 68, 132, 1): (2, 160, 97), (600, 65, 64, 1): (3, 224, 152), (1000, 160, 36, 0): (4, 256, 232), (2049, 36, 20, 1): (9, 256, 1),
+}
+TN_EMPTY = (131073, 4, 4, 1)          # the cap of 512 splits of 288 rows: the last 56 own no rows
+COL_SUM_R = {1: 1, 5: 1, 512: 1, 513: 2, 1030: 3, 2049: 5}          # R -> splits of hpfg_col_sum2
+COL_SUM_M = (1, 64, 65, 129)
+COL_SUM_CAP = (131073, 4, 256)                                        # R, M, splits: the cap
+RELU_BWD_N = (1, 255, 257, 4099)
+
+
+@functools.lru_cache(maxsize=None)
+def tn_case(R, N, K):
+    """dY [R,N], X [R,K] (float32, read-only), the laws dW = dY^T X and db = column sums of dY, and the tolerances: dW by the split-bf16
+    rule, db by bound_8x against torch's float32 sum."""
+    g = torch.Generator().manual_seed(7 * R + 131 * N + K)
+    dy, x = chan_affine((R, N), 0, g), chan_affine((R, K), 0, g)
+    dw, db = dy.double().t() @ x.double(), dy.double().sum(0)
+    tol_dw = gemm_tolerance("bf16x3", dw, dy.t() @ x, _prod3(dy.t().contiguous(), x))
+    return dict(dy=dy, x=x, dw=dw, db=db, tol_dw=tol_dw, tol_db=bound_8x(db, dy.sum(0)), old_dw=bound_8x(dw, dy.t() @ x, 64.0))
+
+
+def tn_mutant(c, mutation, per):
+    """-> (dW, db) of a wrong variant: db from the first 64-wide n-tile only, or the rows of the last split (from (S - 1) * per on) left out"""
+    assert mutation in TN_MUTATIONS, mutation
+    dy, x = c["dy"].double(), c["x"].double()
+    if mutation == "db_first_tile_only":
+        db = c["db"].clone()
+        db[64:] = 0
+        return c["dw"], db
+    r = (-(-dy.shape[0] // per) - 1) * per
+    return dy[:r].t() @ x[:r], dy[:r].sum(0)
+
+
+def relu_bwd_case(n):
+    """y with 0.0, -0.0, a denormal, a negative value, +inf and NaN among random values, dy random: -> (y, dy, dy if y > 0 else 0) float32"""
+    g = torch.Generator().manual_seed(n)
+    y, dy = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    special = torch.tensor([0.0, -0.0, 1e-40, -1.5, float("inf"), float("nan")])[:n]
+    y[torch.randperm(n, generator=g)[:len(special)]] = special
+    return y, dy, torch.where(y > 0, dy, torch.zeros_like(dy))
+
+
+POOL_MUTATIONS = ("bin_end_floor", "gap_mean_of_bin_means", "bwd_divides_by_hw")
+# (N, H, W, C, S, pstride)
+POOL_CASES = ((2, 8, 8, 4, 4, 4), (2, 7, 5, 3, 4, 3), (1, 4, 4, 5, 4, 8), (2, 9, 6, 260, 2, 260), (1, 5, 7, 257, 3, 257), (1, 6, 6, 1024, 1, 1024),
+              (1, 70, 66, 4, 2, 4), (3, 14, 14, 256, 4, 256))
+
+
+def pool_bins(L_, S, mutation=None):
+    """AdaptiveAvgPool's bins of an extent L_: [floor(i L / S), ceil((i + 1) L / S))"""
+    if mutation == "bin_end_floor":
+        return [(i * L_ // S, max((i + 1) * L_ // S, i * L_ // S + 1)) for i in range(S)]
+    return [(i * L_ // S, -(-(i + 1) * L_ // S)) for i in range(S)]
+
+
+def neck_pool_f64(x, S, mutation=None):
+    """x [N,H,W,C] -> (gap [N,C] = the mean over the image, pool [N,S*S,C] = the mean over bin (by, bx) at index by S + bx), float64"""
+    x = x.double()
+    N, Hh, W, C_ = x.shape
+    pool = torch.stack([x[:, y0:y1, x0:x1].mean((1, 2)) for y0, y1 in pool_bins(Hh, S, mutation) for x0, x1 in pool_bins(W, S, mutation)], 1)
+    gap = pool.mean(1) if mutation == "gap_mean_of_bin_means" else x.mean((1, 2))
+    return gap, pool
+
+
+def neck_pool_bwd_f64(dgap, dpool, N, Hh, W, C_, S, mutation=None):
+    """dx [N,H,W,C] = dgap / (H W) + sum over the bins that hold the pixel of dpool / bin size; either gradient may be None"""
+    dx = torch.zeros(N, Hh, W, C_, dtype=torch.float64)
+    if dgap is not None:
+        dx += dgap.double()[:, None, None, :] / (Hh * W)
+    if dpool is not None:
+        b = 0
+        for y0, y1 in pool_bins(Hh, S):
+            for x0, x1 in pool_bins(W, S):
+                size = Hh * W if mutation == "bwd_divides_by_hw" else (y1 - y0) * (x1 - x0)
+                dx[:, y0:y1, x0:x1] += dpool.double()[:, b, None, None, :] / size
+                b += 1
+    return dx
+
+
+@functools.lru_cache(maxsize=None)
+def pool_case(N, Hh, W, C_, S):
+    """x, dgap, dpool (float32, read-only), the forward and backward laws, torch's float32 adaptive_avg_pool2d and its autograd"""
+    g = torch.Generator().manual_seed(10007 * Hh + 101 * W + C_ + S + N)
+    x, dgap, dpool = chan_affine((N, Hh, W, C_), 0, g), chan_affine((N, C_), 0, g), chan_affine((N, S * S, C_), 0, g)
+    gap, pool = neck_pool_f64(x, S)
+    xn = x.permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    g32, p32 = F.adaptive_avg_pool2d(xn, 1), F.adaptive_avg_pool2d(xn, S)
+    c = dict(x=x, dgap=dgap, dpool=dpool, gap=gap, pool=pool, gap32=g32.detach().reshape(N, C_), pool32=p32.detach().reshape(N, C_, S * S).transpose(1, 2))
+    for which, (a, b) in dict(gap=(dgap, None), pool=(None, dpool), both=(dgap, dpool)).items():
+        out = sum(t for t in ((g32.reshape(N, C_) * a).sum() if a is not None else None,
+                              (p32.reshape(N, C_, S * S).transpose(1, 2) * b).sum() if b is not None else None) if t is not None)
+        c["dx_" + which] = neck_pool_bwd_f64(a, b, N, Hh, W, C_, S)
+        c["dx32_" + which] = torch.autograd.grad(out, xn, retain_graph=True)[0].permute(0, 2, 3, 1)
+    return c
+
+
+L2NORM_MUTATIONS = ("eps_added_to_norm", "bwd_without_projection")
+L2NORM_CASES = ((3, 5, 1), (2, 64, 3), (2, 65, 7), (5, 128, 16), (1, 200, 1))          # (G, D, S)
+L2NORM_LAYOUTS = ("ds", "sd")          # memory [G][D][S]: (sd, ss) = (S, 1);  memory [G][S][D]: (sd, ss) = (1, D)
+L2NORM_EPS = 1e-12
+
+
+def l2norm_f64(x, mutation=None):
+    """F.normalize(x, dim=1) of x [G,D,S] -> (u, norms [G,S]), norms = max(||x||_2 over D, 1e-12)"""
+    x = x.double()
+    nrm = torch.sqrt((x * x).sum(1))
+    if mutation == "eps_added_to_norm":
+        return x / (nrm + L2NORM_EPS)[:, None], nrm + L2NORM_EPS
+    nrm = nrm.clamp(min=L2NORM_EPS)
+    return x / nrm[:, None], nrm
+
+
+def l2norm_bwd_f64(du, u, norms, scale=1.0, mutation=None):
+    """dx = scale (du - u <u, du>) / norm per (g, s) column.  (Where the clamp holds, u = 0 and this is scale du / 1e-12: the gradient of
+    x / 1e-12.)"""
+    du, u = du.double(), u.double()
+    dot = 0.0 if mutation == "bwd_without_projection" else (u * du).sum(1, keepdim=True)
+    return scale * (du - u * dot) / norms.double()[:, None]
+
+
+def l2norm_layout(t, layout):
+    """logical [G,D,S] -> the flat memory image of that layout (and back with l2norm_unlayout)"""
+    return (t if layout == "ds" else t.permute(0, 2, 1)).contiguous().view(-1)
+
+
+def l2norm_unlayout(flat, G, D, S, layout):
+    return flat.view(G, D, S) if layout == "ds" else flat.view(G, S, D).permute(0, 2, 1)
+
+
+L2NORM_SPECIAL = (None, "zero", "tiny")
+
+
+@functools.lru_cache(maxsize=None)
+def l2norm_case(G, D, S, special=None):
+    """x, du [G,D,S] float32 (read-only); laws u, norms, dx (scale 1; dx is linear in scale); torch's float32 F.normalize and its autograd.
+    special: column (0, :, 0) of x is zero (the clamp's case: u = 0, norm = 1e-12, dx = du / 1e-12) or has the norm 3e-12 (just above the
+    clamp, where x / (norm + eps) is a quarter short); that column's gradient is 1e12 times the others', so it is compared on its own."""
+    assert special in L2NORM_SPECIAL
+    g = torch.Generator().manual_seed(97 * G + 13 * D + S)
+    x, du = chan_affine((G, S, D), 0, g).permute(0, 2, 1).contiguous(), torch.randn(G, D, S, generator=g)
+    if special == "zero":
+        x[0, :, 0] = 0.0
+    elif special == "tiny":
+        x[0, :, 0] *= float(3e-12 / torch.sqrt((x[0, :, 0].double() ** 2).sum()))
+    u, norms = l2norm_f64(x)
+    xr = x.clone().requires_grad_(True)
+    u32 = F.normalize(xr, dim=1)
+    dx32 = torch.autograd.grad((u32 * du).sum(), xr)[0]
+    n32 = torch.linalg.vector_norm(x, dim=1).clamp(min=L2NORM_EPS)
+    return dict(x=x, du=du, u=u, norms=norms, dx=l2norm_bwd_f64(du, u, norms), u32=u32.detach(), norms32=n32, dx32=dx32, special=special)
+
+
+def l2norm_parts(c, t):
+    """t [G,D,S] or [G,S] of an l2norm_case -> the parts compared on their own: [t] or, with a special column, [that column, the rest]"""
+    if c["special"] is None:
+        return [t]
+    keep = torch.ones(t.shape[0], t.shape[-1], dtype=torch.bool)
+    keep[0, 0] = False
+    cols = t.permute(0, 2, 1) if t.dim() == 3 else t          # [G,S,D] or [G,S]
+    return [p for p in (cols[0, 0], cols[keep]) if p.numel()]
+
+
+NTXENT_MUTATIONS = ("diagonal_in_denominator", "positive_without_wrap", "mean_over_n_rows", "q_without_transpose")
+NTXENT_N = (1, 2, 3, 32, 127, 128)
+NTXENT_T = ((0.7, 16), (0.07, 1))          # (temperature, S): rows of S unit pieces, Gram diagonal S
+NTXENT_FAMILIES = ("independent", "near_copy", "nonsymmetric")
+
+
+def ntxent_f64(G, n, T, mutation=None, dtype=torch.float64):
+    """NT-Xent from the Gram matrix G [2n,2n] of [student ; teacher] rows, read as stored: E = exp(G / T) with the diagonal masked out,
+    denom_i = sum_j E_ij, p(i) = (i + n) mod 2n, loss = mean_i (log denom_i - G[i,p(i)] / T);  dL/dG_ij = (E_ij / denom_i - [j = p(i)]) / (2n T)
+    and Q = (dL/dG + its transpose)[:n].  -> (loss, Q [n,2n], largest term max_i max(|log denom_i|, |G[i,p(i)]| / T)).  dtype=torch.float32:
+    the yardstick (diagonal excluded by masking, as the reference's masked_select: sum - diagonal cancels to 0 at S = 16).  T is the float32
+    the kernel is handed."""
+    assert mutation is None or mutation in NTXENT_MUTATIONS, mutation
+    m = 2 * n
+    G = G.to(dtype)
+    Tt = torch.tensor(f32_exact(T), dtype=dtype)
+    eye = torch.eye(m, dtype=torch.bool)
+    E = torch.exp(G / Tt)
+    if mutation != "diagonal_in_denominator":
+        E = E.masked_fill(eye, 0.0)
+    denom = E.sum(1)
+    i = torch.arange(m)
+    p = (i + n) % m
+    if mutation == "positive_without_wrap":          # the flat index i m + i + n: past the row for the teacher rows, past the matrix for the last
+        pos = torch.cat([G.reshape(-1), torch.zeros(m, dtype=dtype)])[i * m + i + n]
+    else:
+        pos = G[i, p]
+    rows = torch.log(denom) - pos / Tt
+    count = n if mutation == "mean_over_n_rows" else m
+    loss = rows.sum() / count
+    P = torch.zeros(m, m, dtype=dtype)
+    P[i, p] = 1.0
+    D = (E.masked_fill(eye, 0.0) / denom[:, None] - P) / (count * Tt)
+    Q = D[:n] if mutation == "q_without_transpose" else (D + D.t())[:n]
+    return loss, Q, float(torch.maximum(torch.log(denom).abs(), (pos / Tt).abs()).max())
+
+
+def ntxent_tolerance(law, yard):
+    """(loss bound, Q bound): the loss is a difference of terms as large as S / T, so its floor is 4 float32 ulp of the largest term, not of
+    the result; Q by bound_8x."""
+    return max(8.0 * abs(float(yard[0]) - float(law[0])), 4.0 * ulp32(law[2])), bound_8x(law[1], yard[1])
+
+
+def _unit_rows(rows, S):
+    """[r, S, d] -> [r, S d] with every piece of d elements normalised (float64)"""
+    rows = rows.double()
+    return (rows / torch.sqrt((rows * rows).sum(-1, keepdim=True))).reshape(rows.shape[0], -1)
+
+
+@functools.lru_cache(maxsize=None)
+def ntxent_case(family, n, T, S, d=8):
+    """The Gram matrix (built in float64 from normalised rows, rounded once to float32), the law, the float32 yardstick and the tolerances.
+    independent: teacher rows drawn apart from the student's (loss of order log 2n).  near_copy: teacher = student + 1e-3 randn (loss near
+    0).  nonsymmetric: independent rows, then every element of the matrix perturbed on its own at the 1e-3 level."""
+    g = torch.Generator().manual_seed(1000 * n + 10 * S + NTXENT_FAMILIES.index(family))
+    a = torch.randn(n, S, d, generator=g, dtype=torch.float64)
+    b = a + 1e-3 * torch.randn(n, S, d, generator=g, dtype=torch.float64) if family == "near_copy" else torch.randn(n, S, d, generator=g, dtype=torch.float64)
+    U = torch.cat([_unit_rows(a, S), _unit_rows(b, S)])
+    G = U @ U.t()
+    if family == "nonsymmetric":
+        G = G * (1.0 + 1e-3 * torch.randn(2 * n, 2 * n, generator=g, dtype=torch.float64))
+    G = G.float()
+    law, yard = ntxent_f64(G, n, T), ntxent_f64(G, n, T, dtype=torch.float32)
+    return dict(G=G, n=n, T=T, law=law, yard=yard, tol=ntxent_tolerance(law, yard))
+
+
+DENSE_N = (1, 3, 32)
+DENSE_D, DENSE_S = 24, 4          # feature width and positions of the dense branch ([n, D] global and [n, D, S] dense features)
+
+
+@functools.lru_cache(maxsize=None)
+def dense_case(n, T=0.7):
+    """Student and teacher features (g [n,D], d [n,D,S], float32), float64 autograd of oracle.losses_ref.dense_loss (value, dg, dd), the same
+    in float32, and the largest term of the two NT-Xent sums (for the value's floor)."""
+    from oracle import losses_ref
+    gen = torch.Generator().manual_seed(555 + n)
+    sg, sd_ = chan_affine((n, DENSE_D), 0, gen), chan_affine((n, DENSE_S, DENSE_D), 0, gen).permute(0, 2, 1).contiguous()
+    tg, td = chan_affine((n, DENSE_D), 0, gen), chan_affine((n, DENSE_S, DENSE_D), 0, gen).permute(0, 2, 1).contiguous()
+    out = {}
+    for dt in (torch.float64, torch.float32):
+        a, b = sg.to(dt).requires_grad_(True), sd_.to(dt).requires_grad_(True)
+        v = losses_ref.dense_loss((a, b), (tg.to(dt), td.to(dt)), T)
+        out[dt] = (v.detach(),) + tuple(t.detach() for t in torch.autograd.grad(v, (a, b)))
+    top = 0.0
+    for s, t in ((sg[:, :, None], tg[:, :, None]), (sd_, td)):
+        U = torch.cat([l2norm_f64(s)[0].flatten(1), l2norm_f64(t)[0].flatten(1)])
+        top = max(top, ntxent_f64((U @ U.t()), n, T)[2])
+    return dict(sg=sg, sd=sd_, tg=tg, td=td, ref=out[torch.float64], yard=out[torch.float32], top=top)
