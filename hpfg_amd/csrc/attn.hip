@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void attn_mfma_fwd_kernel(const float* __restr
   stage_kv<D>(kv, b, h, M, C, 1, nullptr, ldsVT, tid);
   __syncthreads();
   const long qi = (long)blockIdx.x * 64 + wave * 16 + (lane & 15);
-  a_bf16x8 qh[KS], ql[KS];
+  bf16x8 qh[KS], ql[KS];
   load_row_frags<D>(q + (long)b * N * C, qi, N, C, h, lane, scale, qh, ql);
   f32x4 p[4], o[DT];
   softmax_t<D>(ldsK, qh, ql, M, lane, NoTerm{}, p);
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void attn_mfma_dq_kernel(const float* __restri
   stage_kv<D>(kv, b, h, M, C, 1, ldsV, nullptr, tid);
   __syncthreads();
   const long qi = (long)blockIdx.x * 64 + wave * 16 + (lane & 15);
-  a_bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
+  bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
   load_row_frags<D>(q + (long)b * N * C, qi, N, C, h, lane, scale, qh, ql);
   load_row_frags<D>(dout + (long)b * N * C, qi, N, C, h, lane, 1.f, dh, dl);
   f32x4 p[4], dp[4], o[DT];
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void attn_mfma_dkv_kernel(const float* __restr
       accK[dt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
   // K / V fragments with the key on the lane (column operand)
-  a_bf16x8 kh[HOLD ? 4 : 1][KS], kl[HOLD ? 4 : 1][KS], vh[HOLD ? 4 : 1][KS], vl[HOLD ? 4 : 1][KS];
+  bf16x8 kh[HOLD ? 4 : 1][KS], kl[HOLD ? 4 : 1][KS], vh[HOLD ? 4 : 1][KS], vl[HOLD ? 4 : 1][KS];
   if constexpr (HOLD) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void attn_mfma_dkv_kernel(const float* __restr
   const float* db = dout + (long)b * N * C;
   for (long base = q0 + wave * 32; base < q1; base += 128) {
     f32x4 s[2][4], dp[2][4];
-    a_bf16x8 qh[2][KS], ql[2][KS], dh[2][KS], dl[2][KS];
+    bf16x8 qh[2][KS], ql[2][KS], dh[2][KS], dl[2][KS];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const long qi = base + 16 * u + (lane & 15);
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void attn_mfma_dkv_kernel(const float* __restr
     // S[q][key] and dP[q][key]: queries 16 u + 4 g + r on the rows, key 16 t + (lane & 15) on the lane
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      a_bf16x8 fkh[KS], fkl[KS], fvh[KS], fvl[KS];
+      bf16x8 fkh[KS], fkl[KS], fvh[KS], fvl[KS];
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         if constexpr (HOLD) {
@@ -144,9 +144,9 @@ __global__ __launch_bounds__(256) void attn_mfma_dkv_kernel(const float* __restr
         s[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
         dp[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) { ATT_MFMA3(s[u][t], qh[u][ks], ql[u][ks], fkh[ks], fkl[ks]) }
+        for (int ks = 0; ks < KS; ++ks) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, s[u][t], qh[u][ks], ql[u][ks], fkh[ks], fkl[ks]) }
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) { ATT_MFMA3(dp[u][t], dh[u][ks], dl[u][ks], fvh[ks], fvl[ks]) }
+        for (int ks = 0; ks < KS; ++ks) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, dp[u][t], dh[u][ks], dl[u][ks], fvh[ks], fvl[ks]) }
       }
     }
     // softmax statistics per query row: 4 tiles x 16 lanes hold a row's 64 scores
@@ -189,15 +189,15 @@ __global__ __launch_bounds__(256) void attn_mfma_dkv_kernel(const float* __restr
     // dV^T[d][key] += dO^T[d][q] P[q][key],  dK^T[d][key] += Q^T[d][q] dS[q][key]   (one contraction step over the wave's 32 queries)
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      a_bf16x8 ph, pl, sh, sl;
+      bf16x8 ph, pl, sh, sl;
       acc_operand(s[0][t], s[1][t], ph, pl);
       acc_operand(dp[0][t], dp[1][t], sh, sl);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const a_bf16x8 oh = trn_frag(myDO, QROW, 16 * dt, 0, lane), ol = trn_frag(myDO + QPL, QROW, 16 * dt, 0, lane);
-        const a_bf16x8 th = trn_frag(myQ, QROW, 16 * dt, 0, lane), tl = trn_frag(myQ + QPL, QROW, 16 * dt, 0, lane);
-        ATT_MFMA3(accV[dt][t], oh, ol, ph, pl)
-        ATT_MFMA3(accK[dt][t], th, tl, sh, sl)
+        const bf16x8 oh = trn_frag(myDO, QROW, 16 * dt, 0, lane), ol = trn_frag(myDO + QPL, QROW, 16 * dt, 0, lane);
+        const bf16x8 th = trn_frag(myQ, QROW, 16 * dt, 0, lane), tl = trn_frag(myQ + QPL, QROW, 16 * dt, 0, lane);
+        { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, accV[dt][t], oh, ol, ph, pl) }
+        { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, accK[dt][t], th, tl, sh, sl) }
       }
     }
   }

@@ -57,19 +57,19 @@ __device__ __forceinline__ void zero_tiles(f32x4 (&a)[N]) {
 // ---- S^T orientation (forward, dQ): keys on the accumulator rows, one query per lane (lane & 15) -----------------------------------------
 // tile t of a natural image times the row whose fragments this lane holds: S^T = K q (bh / bl = the scaled query) or dP^T = V dO
 template <int D>
-__device__ __forceinline__ void tile_t(const unsigned char* img, int t, const a_bf16x8 (&bh)[Geo<D>::KS], const a_bf16x8 (&bl)[Geo<D>::KS], int lane,
+__device__ __forceinline__ void tile_t(const unsigned char* img, int t, const bf16x8 (&bh)[Geo<D>::KS], const bf16x8 (&bl)[Geo<D>::KS], int lane,
                                        f32x4& acc) {
   acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int ks = 0; ks < Geo<D>::KS; ++ks) {
-    const a_bf16x8 ah = nat_frag<D>(img, 16 * t, ks, lane), al = nat_frag<D>(img + Geo<D>::KPLANE, 16 * t, ks, lane);
-    ATT_MFMA3(acc, ah, al, bh[ks], bl[ks])
+    const bf16x8 ah = nat_frag<D>(img, 16 * t, ks, lane), al = nat_frag<D>(img + Geo<D>::KPLANE, 16 * t, ks, lane);
+    { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc, ah, al, bh[ks], bl[ks]) }
   }
 }
 
 // the four score tiles p[0..3] of one K image (keys key0 ..): p[t][r] = logit of key key0 + 16 t + 4 g + r for the query on this lane; mx = running maximum
 template <int D, class Term>
-__device__ __forceinline__ void scores_t(const unsigned char* ldsK, const a_bf16x8 (&qh)[Geo<D>::KS], const a_bf16x8 (&ql)[Geo<D>::KS], int key0, int M,
+__device__ __forceinline__ void scores_t(const unsigned char* ldsK, const bf16x8 (&qh)[Geo<D>::KS], const bf16x8 (&ql)[Geo<D>::KS], int key0, int M,
                                          int lane, Term term, f32x4* p, float& mx) {
   const int g = lane >> 4;
 #pragma unroll
@@ -108,7 +108,7 @@ __device__ __forceinline__ void softmax_finish_t(f32x4* p, int M, int lane, floa
 
 // one image of at most 64 keys: probabilities p[t][r] of key 16 t + 4 g + r for the query on this lane
 template <int D, class Term>
-__device__ __forceinline__ void softmax_t(const unsigned char* ldsK, const a_bf16x8 (&qh)[Geo<D>::KS], const a_bf16x8 (&ql)[Geo<D>::KS], int M,
+__device__ __forceinline__ void softmax_t(const unsigned char* ldsK, const bf16x8 (&qh)[Geo<D>::KS], const bf16x8 (&ql)[Geo<D>::KS], int M,
                                           int lane, Term term, f32x4 (&p)[4]) {
   float mx = NEG, den;
   scores_t<D>(ldsK, qh, ql, 0, M, lane, term, p, mx);
@@ -117,7 +117,7 @@ __device__ __forceinline__ void softmax_t(const unsigned char* ldsK, const a_bf1
 
 // dp = dS^T = P .* (dP^T - rowsum(P .* dP)) with dP^T = V dO
 template <int D>
-__device__ __forceinline__ void ds_t(const unsigned char* ldsV, const a_bf16x8 (&dh)[Geo<D>::KS], const a_bf16x8 (&dl)[Geo<D>::KS], int lane,
+__device__ __forceinline__ void ds_t(const unsigned char* ldsV, const bf16x8 (&dh)[Geo<D>::KS], const bf16x8 (&dl)[Geo<D>::KS], int lane,
                                      const f32x4 (&p)[4], f32x4 (&dp)[4]) {
   float delta = 0.f;
 #pragma unroll
@@ -139,12 +139,12 @@ template <int D>
 __device__ __forceinline__ void mul_trn(const f32x4* a, const unsigned char* trn, int lane, f32x4 (&o)[Geo<D>::DT]) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    a_bf16x8 ah, al;
+    bf16x8 ah, al;
     acc_operand(a[2 * s], a[2 * s + 1], ah, al);
 #pragma unroll
     for (int dt = 0; dt < Geo<D>::DT; ++dt) {
-      const a_bf16x8 fh = trn_frag(trn, TROW, 16 * dt, s, lane), fl = trn_frag(trn + Geo<D>::TPL, TROW, 16 * dt, s, lane);
-      ATT_MFMA3(o[dt], fh, fl, ah, al)
+      const bf16x8 fh = trn_frag(trn, TROW, 16 * dt, s, lane), fl = trn_frag(trn + Geo<D>::TPL, TROW, 16 * dt, s, lane);
+      { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, o[dt], fh, fl, ah, al) }
     }
   }
 }

@@ -1,14 +1,12 @@
-// Fragment helpers of the attention kernels on the matrix cores: the LDS image geometry, the split-bf16 conversion and the fragment loaders.
-// attn_core.h builds the kernels' phases on them and documents the lane layouts at its top.
+// Fragment helpers of the attention kernels on the matrix cores: the LDS image geometry and the fragment loaders.  The arithmetic -- the
+// vector types, the hi / lo split (split8v) and the three-issue product (HPFG_MFMA3, the first operand's lo first) -- is bf16x3.h's, shared with
+// the convolutions and the GEMMs.  attn_core.h builds the kernels' phases on them and documents the lane layouts at its top.
 #pragma once
-#include "common.h"
+#include "bf16x3.h"
 
 namespace {
 
-typedef __bf16 a_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 a_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 a_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float a_f32x2 __attribute__((ext_vector_type(2)));
+using namespace hpfg_bf16x3;
 
 constexpr int MK = 64;                         // keys of one LDS image (attn.hip, attn_window.hip: the maximum; attn_keys.hip: one key block)
 constexpr int TROW = 144;                      // bytes per row of a [D d][64 keys] bf16 image (128 B + 16 B pad)
@@ -20,26 +18,6 @@ template <int D> struct Geo {
   static constexpr int KPLANE = MK * KROW, TPL = D * TROW, QPL = D * QROW;
 };
 constexpr float NEG = -3.0e38f;
-
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& hw, uint32_t& lw) {
-  const a_bf16x2 h = __builtin_convertvector(a_f32x2{x0, x1}, a_bf16x2);
-  hw = __builtin_bit_cast(uint32_t, h);
-  const a_f32x2 hf = {__builtin_bit_cast(float, hw << 16), __builtin_bit_cast(float, hw & 0xFFFF0000u)};
-  lw = __builtin_bit_cast(uint32_t, __builtin_convertvector(a_f32x2{x0, x1} - hf, a_bf16x2));
-}
-__device__ __forceinline__ void split8v(const float (&v)[8], a_bf16x8& hi, a_bf16x8& lo) {
-  uint32_t h[4], l[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) split2(v[2 * k], v[2 * k + 1], h[k], l[k]);
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  hi = __builtin_bit_cast(a_bf16x8, (u32x4{h[0], h[1], h[2], h[3]}));
-  lo = __builtin_bit_cast(a_bf16x8, (u32x4{l[0], l[1], l[2], l[3]}));
-}
-
-#define ATT_MFMA3(ACC, AH, AL, BH, BL)                                \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, BH, ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AL, BH, ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AH, BL, ACC, 0, 0, 0);
 
 // (stage_win of attn_window.hip is this text with the window's token table; why the two are not one function: top of attn_core.h)
 // rows [key][D d] of k or v (which = 0 / 1) of one (image, head) -> natural image [64][D] (hi, lo) and / or transposed image [D][64].
@@ -57,11 +35,11 @@ __device__ __forceinline__ void stage_kv(const float* __restrict__ kv, int b, in
       const f32x4 a = *reinterpret_cast<const f32x4*>(p), c = *reinterpret_cast<const f32x4*>(p + 4);
       v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = c[0]; v[5] = c[1]; v[6] = c[2]; v[7] = c[3];
     }
-    a_bf16x8 hi, lo;
+    bf16x8 hi, lo;
     split8v(v, hi, lo);
     if (nat) {
-      *reinterpret_cast<a_bf16x8*>(nat + key * KROW + d0 * 2) = hi;
-      *reinterpret_cast<a_bf16x8*>(nat + key * KROW + d0 * 2 + KPLANE) = lo;
+      *reinterpret_cast<bf16x8*>(nat + key * KROW + d0 * 2) = hi;
+      *reinterpret_cast<bf16x8*>(nat + key * KROW + d0 * 2 + KPLANE) = lo;
     }
     if (trn) {
 #pragma unroll
@@ -75,15 +53,15 @@ __device__ __forceinline__ void stage_kv(const float* __restrict__ kv, int b, in
 
 // fragment of a natural [rows][D d] image for k-step ks: row = row0 + (lane & 15), 8 consecutive d of k-group lane >> 4 (d = 32 ks + 8 g ..)
 template <int D>
-__device__ __forceinline__ a_bf16x8 nat_frag(const unsigned char* plane, int row0, int ks, int lane) {
-  return *reinterpret_cast<const a_bf16x8*>(plane + (row0 + (lane & 15)) * Geo<D>::KROW + ks * 64 + (lane >> 4) * 16);
+__device__ __forceinline__ bf16x8 nat_frag(const unsigned char* plane, int row0, int ks, int lane) {
+  return *reinterpret_cast<const bf16x8*>(plane + (row0 + (lane & 15)) * Geo<D>::KROW + ks * 64 + (lane >> 4) * 16);
 }
 // fragment of a transposed [D d][64 pos] image for contraction step s over 32 positions, in the accumulator-operand order: this lane's
 // positions are 32 s + 4 g + {0..3} and 32 s + 16 + 4 g + {0..3} (g = lane >> 4), row = d0 + (lane & 15)
-__device__ __forceinline__ a_bf16x8 trn_frag(const unsigned char* plane, int rowbytes, int d0, int s, int lane) {
+__device__ __forceinline__ bf16x8 trn_frag(const unsigned char* plane, int rowbytes, int d0, int s, int lane) {
   const unsigned char* p = plane + (d0 + (lane & 15)) * rowbytes + (32 * s + 4 * (lane >> 4)) * 2;
-  const a_bf16x4 a = *reinterpret_cast<const a_bf16x4*>(p), b = *reinterpret_cast<const a_bf16x4*>(p + 32);
-  return a_bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  const bf16x4 a = *reinterpret_cast<const bf16x4*>(p), b = *reinterpret_cast<const bf16x4*>(p + 32);
+  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
 // this lane's 8 head-dim values of k-step ks (k-group lane >> 4) of row `row` of a [.., heads, D] tensor, times `mul`; zeros beyond `nrows`
@@ -102,7 +80,7 @@ __device__ __forceinline__ void load_row8(const float* __restrict__ base, long r
 // one row's D values as the split-bf16 fragments of its KS k-steps
 template <int D>
 __device__ __forceinline__ void load_row_frags(const float* __restrict__ base, long row, long nrows, int C, int h, int lane, float mul,
-                                               a_bf16x8 (&hi)[Geo<D>::KS], a_bf16x8 (&lo)[Geo<D>::KS]) {
+                                               bf16x8 (&hi)[Geo<D>::KS], bf16x8 (&lo)[Geo<D>::KS]) {
 #pragma unroll
   for (int ks = 0; ks < Geo<D>::KS; ++ks) {
     float v[8];
@@ -112,9 +90,8 @@ __device__ __forceinline__ void load_row_frags(const float* __restrict__ base, l
 }
 
 // accumulator tiles (2 s, 2 s + 1) -> split-bf16 B operand of contraction step s
-__device__ __forceinline__ void acc_operand(const f32x4& a, const f32x4& b, a_bf16x8& hi, a_bf16x8& lo) {
-  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  split8v(v, hi, lo);
+__device__ __forceinline__ void acc_operand(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
+  split8(a, b, hi, lo);
 }
 
 }  // namespace

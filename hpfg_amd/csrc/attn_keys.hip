@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void attn_keys_fwd_kernel(const float* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
   const int b = blockIdx.z, h = blockIdx.y, C = heads * D;
   const long qi = (long)blockIdx.x * 64 + wave * 16 + (lane & 15);
-  a_bf16x8 qh[KS], ql[KS];
+  bf16x8 qh[KS], ql[KS];
   load_row_frags<D>(q + (long)b * N * C, qi, N, C, h, lane, scale, qh, ql);
   // S^T tiles of every key block: p[4 kb + t][r] = score of key 64 kb + 16 t + 4 g + r for the query on this lane
   f32x4 p[4 * NB], o[DT];
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void attn_keys_dq_kernel(const float* __restri
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
   const int b = blockIdx.z, h = blockIdx.y, C = heads * D;
   const long qi = (long)blockIdx.x * 64 + wave * 16 + (lane & 15);
-  a_bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
+  bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
   load_row_frags<D>(q + (long)b * N * C, qi, N, C, h, lane, scale, qh, ql);
   load_row_frags<D>(dout + (long)b * N * C, qi, N, C, h, lane, 1.f, dh, dl);
   float delta = 0.f;                             // fp32 on the unsplit values: this lane's 8 KS head-dim positions, then the four k-groups
@@ -109,13 +109,13 @@ __global__ __launch_bounds__(256) void attn_keys_dq_kernel(const float* __restri
       f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const a_bf16x8 kh = nat_frag<D>(ldsK, 16 * t, ks, lane), kl = nat_frag<D>(ldsK + KPLANE, 16 * t, ks, lane);
-        ATT_MFMA3(s, kh, kl, qh[ks], ql[ks])     // S^T[key][q]
+        const bf16x8 kh = nat_frag<D>(ldsK, 16 * t, ks, lane), kl = nat_frag<D>(ldsK + KPLANE, 16 * t, ks, lane);
+        { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, s, kh, kl, qh[ks], ql[ks]) }     // S^T[key][q]
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const a_bf16x8 vh = nat_frag<D>(ldsV, 16 * t, ks, lane), vl = nat_frag<D>(ldsV + KPLANE, 16 * t, ks, lane);
-        ATT_MFMA3(dp, vh, vl, dh[ks], dl[ks])    // dP^T[key][q]
+        const bf16x8 vh = nat_frag<D>(ldsV, 16 * t, ks, lane), vl = nat_frag<D>(ldsV + KPLANE, 16 * t, ks, lane);
+        { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, dp, vh, vl, dh[ks], dl[ks]) }    // dP^T[key][q]
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -125,12 +125,12 @@ __global__ __launch_bounds__(256) void attn_keys_dq_kernel(const float* __restri
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      a_bf16x8 sh, sl;
+      bf16x8 sh, sl;
       acc_operand(ds[2 * s], ds[2 * s + 1], sh, sl);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const a_bf16x8 kh = trn_frag(ldsKT, TROW, 16 * dt, s, lane), kl = trn_frag(ldsKT + TPL, TROW, 16 * dt, s, lane);
-        ATT_MFMA3(o[dt], kh, kl, sh, sl)          // dQ^T[d][q] / scale
+        const bf16x8 kh = trn_frag(ldsKT, TROW, 16 * dt, s, lane), kl = trn_frag(ldsKT + TPL, TROW, 16 * dt, s, lane);
+        { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, o[dt], kh, kl, sh, sl) }          // dQ^T[d][q] / scale
       }
     }
   }
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void attn_keys_dkv_kernel(const float* __restr
   const float* eb = delta + ((long)b * heads + h) * N;
   for (long base = q0 + wave * 32; base < q1; base += 128) {
     f32x4 s[2][4], dp[2][4];
-    a_bf16x8 qh[2][KS], ql[2][KS], dh[2][KS], dl[2][KS];
+    bf16x8 qh[2][KS], ql[2][KS], dh[2][KS], dl[2][KS];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const long qi = base + 16 * u + (lane & 15);
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void attn_keys_dkv_kernel(const float* __restr
     // S[q][key] and dP[q][key]: queries 16 u + 4 g + r on the rows, key 64 kb + 16 t + (lane & 15) on the lane
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      a_bf16x8 fkh[KS], fkl[KS], fvh[KS], fvl[KS];
+      bf16x8 fkh[KS], fkl[KS], fvh[KS], fvl[KS];
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         fkh[ks] = nat_frag<D>(ldsK, 16 * t, ks, lane);
@@ -209,9 +209,9 @@ __global__ __launch_bounds__(256) void attn_keys_dkv_kernel(const float* __restr
         s[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
         dp[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) { ATT_MFMA3(s[u][t], qh[u][ks], ql[u][ks], fkh[ks], fkl[ks]) }
+        for (int ks = 0; ks < KS; ++ks) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, s[u][t], qh[u][ks], ql[u][ks], fkh[ks], fkl[ks]) }
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) { ATT_MFMA3(dp[u][t], dh[u][ks], dl[u][ks], fvh[ks], fvl[ks]) }
+        for (int ks = 0; ks < KS; ++ks) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, dp[u][t], dh[u][ks], dl[u][ks], fvh[ks], fvl[ks]) }
       }
     }
     // P = exp(S - lse), dS = P (dP - delta); rows beyond the range and keys beyond M contribute exact zeros
@@ -232,15 +232,15 @@ __global__ __launch_bounds__(256) void attn_keys_dkv_kernel(const float* __restr
     // dV^T[d][key] += dO^T[d][q] P[q][key],  dK^T[d][key] += Q^T[d][q] dS[q][key]   (one contraction step over the wave's 32 queries)
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      a_bf16x8 ph, pl, sh, sl;
+      bf16x8 ph, pl, sh, sl;
       acc_operand(s[0][t], s[1][t], ph, pl);
       acc_operand(dp[0][t], dp[1][t], sh, sl);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const a_bf16x8 oh = trn_frag(myDO, QROW, 16 * dt, 0, lane), ol = trn_frag(myDO + QPL, QROW, 16 * dt, 0, lane);
-        const a_bf16x8 th = trn_frag(myQ, QROW, 16 * dt, 0, lane), tl = trn_frag(myQ + QPL, QROW, 16 * dt, 0, lane);
-        ATT_MFMA3(accV[dt][t], oh, ol, ph, pl)
-        ATT_MFMA3(accK[dt][t], th, tl, sh, sl)
+        const bf16x8 oh = trn_frag(myDO, QROW, 16 * dt, 0, lane), ol = trn_frag(myDO + QPL, QROW, 16 * dt, 0, lane);
+        const bf16x8 th = trn_frag(myQ, QROW, 16 * dt, 0, lane), tl = trn_frag(myQ + QPL, QROW, 16 * dt, 0, lane);
+        { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, accV[dt][t], oh, ol, ph, pl) }
+        { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, accK[dt][t], th, tl, sh, sl) }
       }
     }
   }

@@ -87,11 +87,11 @@ __device__ __forceinline__ void stage_win(const float* __restrict__ img, const i
       const f32x4 a = *reinterpret_cast<const f32x4*>(p), c = *reinterpret_cast<const f32x4*>(p + 4);
       v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = c[0]; v[5] = c[1]; v[6] = c[2]; v[7] = c[3];
     }
-    a_bf16x8 hi, lo;
+    bf16x8 hi, lo;
     split8v(v, hi, lo);
     if (nat) {
-      *reinterpret_cast<a_bf16x8*>(nat + key * KROW + d0 * 2) = hi;
-      *reinterpret_cast<a_bf16x8*>(nat + key * KROW + d0 * 2 + KPLANE) = lo;
+      *reinterpret_cast<bf16x8*>(nat + key * KROW + d0 * 2) = hi;
+      *reinterpret_cast<bf16x8*>(nat + key * KROW + d0 * 2 + KPLANE) = lo;
     }
     if (trn) {
 #pragma unroll
@@ -140,7 +140,7 @@ __device__ __forceinline__ void drop_factors_t(const Drop& dr, uint32_t sd, uint
 
 // ds_t of attn_core.h with dP masked before the row sum
 template <int D>
-__device__ __forceinline__ void ds_drop_t(const unsigned char* ldsV, const a_bf16x8 (&dh)[Geo<D>::KS], const a_bf16x8 (&dl)[Geo<D>::KS], int lane,
+__device__ __forceinline__ void ds_drop_t(const unsigned char* ldsV, const bf16x8 (&dh)[Geo<D>::KS], const bf16x8 (&dl)[Geo<D>::KS], int lane,
                                           const f32x4 (&p)[4], const f32x4 (&f)[4], f32x4 (&dp)[4]) {
   float delta = 0.f;
 #pragma unroll
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void attn_window_fwd_kernel(const float* __res
   stage_win<D, 256>(img, tok, C3, 2 * C + h * D, nullptr, ldsVT, tid);
   __syncthreads();
   const int l1 = wave * 16 + (lane & 15), t1 = tok[l1];
-  a_bf16x8 qh[KS], ql[KS];
+  bf16x8 qh[KS], ql[KS];
   load_row_frags<D>(img, t1 >= 0 ? t1 : HW, HW, C3, h, lane, scale, qh, ql);
   f32x4 p[4], o[DT];
   softmax_t<D>(ldsK, qh, ql, gm.L(), lane, WinTerm{rel[l1], rel, bias, gm.c0()}, p);
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void attn_window_dq_kernel(const float* __rest
   stage_win<D, 256>(img, tok, C3, 2 * C + h * D, ldsV, nullptr, tid);
   __syncthreads();
   const int l1 = wave * 16 + (lane & 15), t1 = tok[l1];
-  a_bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
+  bf16x8 qh[KS], ql[KS], dh[KS], dl[KS];
   load_row_frags<D>(img, t1 >= 0 ? t1 : HW, HW, C3, h, lane, scale, qh, ql);
   load_row_frags<D>(dout + (long)b * HW * C, t1 >= 0 ? t1 : HW, HW, C, h, lane, 1.f, dh, dl);
   f32x4 p[4], dp[4], o[DT];
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(128) void attn_window_dkv_kernel(const float* __res
     }
   const int base = wave * 32;
   f32x4 s[2][4], dp[2][4];
-  a_bf16x8 qh[2][KS], ql[2][KS], dh[2][KS], dl[2][KS];
+  bf16x8 qh[2][KS], ql[2][KS], dh[2][KS], dl[2][KS];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int tq = tok[base + 16 * u + (lane & 15)];
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(128) void attn_window_dkv_kernel(const float* __res
   // S[q][key] and dP[q][key]: queries base + 16 u + 4 g + r on the rows, key 16 t + (lane & 15) on the lane
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    a_bf16x8 fkh[KS], fkl[KS], fvh[KS], fvl[KS];
+    bf16x8 fkh[KS], fkl[KS], fvh[KS], fvl[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       fkh[ks] = nat_frag<D>(ldsK, 16 * t, ks, lane);
@@ -326,9 +326,9 @@ __global__ __launch_bounds__(128) void attn_window_dkv_kernel(const float* __res
       s[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
       dp[u][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) { ATT_MFMA3(s[u][t], qh[u][ks], ql[u][ks], fkh[ks], fkl[ks]) }
+      for (int ks = 0; ks < KS; ++ks) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, s[u][t], qh[u][ks], ql[u][ks], fkh[ks], fkl[ks]) }
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) { ATT_MFMA3(dp[u][t], dh[u][ks], dl[u][ks], fvh[ks], fvl[ks]) }
+      for (int ks = 0; ks < KS; ++ks) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, dp[u][t], dh[u][ks], dl[u][ks], fvh[ks], fvl[ks]) }
 #pragma unroll
       for (int r = 0; r < 4; ++r) s[u][t][r] = key < L ? logit_add(s[u][t][r], rel[base + 16 * u + 4 * g + r], rk, c0, bias) : NEG;
     }
@@ -377,15 +377,15 @@ __global__ __launch_bounds__(128) void attn_window_dkv_kernel(const float* __res
   // dV^T[d][key] += dO^T[d][q] P[q][key],  dK^T[d][key] += Q^T[d][q] dS[q][key]   (one contraction step over the wave's 32 queries)
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    a_bf16x8 ph, pl, sh, sl;
+    bf16x8 ph, pl, sh, sl;
     acc_operand(s[0][t], s[1][t], ph, pl);
     acc_operand(dp[0][t], dp[1][t], sh, sl);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
-      const a_bf16x8 oh = trn_frag(myDO, QROW, 16 * dt, 0, lane), ol = trn_frag(myDO + QPL, QROW, 16 * dt, 0, lane);
-      const a_bf16x8 th = trn_frag(myQ, QROW, 16 * dt, 0, lane), tl = trn_frag(myQ + QPL, QROW, 16 * dt, 0, lane);
-      ATT_MFMA3(accV[dt][t], oh, ol, ph, pl)
-      ATT_MFMA3(accK[dt][t], th, tl, sh, sl)
+      const bf16x8 oh = trn_frag(myDO, QROW, 16 * dt, 0, lane), ol = trn_frag(myDO + QPL, QROW, 16 * dt, 0, lane);
+      const bf16x8 th = trn_frag(myQ, QROW, 16 * dt, 0, lane), tl = trn_frag(myQ + QPL, QROW, 16 * dt, 0, lane);
+      { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, accV[dt][t], oh, ol, ph, pl) }
+      { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, accK[dt][t], th, tl, sh, sl) }
     }
   }
   // add the two waves in a fixed order (wave 0 stores, wave 1 adds): [2][64 keys][D d]; accumulator rows = d (4 g + r), column = key.

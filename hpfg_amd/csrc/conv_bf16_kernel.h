@@ -277,11 +277,6 @@ __device__ __forceinline__ void conv16_flush_stats(const HpfgConvArgs& p, f32x4 
   }
 }
 
-#define HPFG16_MFMA3(ACC, AH, AL, BH, BL)                              \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BH, AH, ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BL, AH, ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BH, AL, ACC, 0, 0, 0);
-
 // Concat loader (KIND == CAT): the upsampled half goes through the LDS patch of stage.h, one chunk of KC channels at a time (the patch piece
 // of a thread is prefetched a chunk ahead like the cheap loaders).  Skip-half chunks are plain BN + LeakyReLU pieces.
 template <class C>
@@ -543,7 +538,7 @@ __global__ __launch_bounds__(256, (wg_per_cu<C, KIND>())) void conv_bf16x3_kerne
           load_b<C>(bh[(s + BD) % BR], bl[(s + BD) % BR], wpk, ksn, ntn, nt0, lane);
         }
 #pragma unroll
-        for (int j = 0; j < C::NI; ++j) { HPFG16_MFMA3(acc[m][j], ah[q % AR], al[q % AR], bh[s % BR][j], bl[s % BR][j]) }
+        for (int j = 0; j < C::NI; ++j) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[m][j], bh[s % BR][j], bl[s % BR][j], ah[q % AR], al[q % AR]) }
         if (FENCE) __builtin_amdgcn_sched_barrier(0x216);   // VALU, SALU, VMEM and DS writes may cross; DS reads and MFMAs may not
       }
       HPFG_TR(6)
@@ -760,7 +755,7 @@ __global__ __launch_bounds__(256) void conv1x1_bf16x3_kernel(HpfgConvArgs p, int
       const bf16x8 ah = *reinterpret_cast<const bf16x8*>(lds + aoff[m]);
       const bf16x8 al = *reinterpret_cast<const bf16x8*>(lds + aoff[m] + C::PLANE);
 #pragma unroll
-      for (int j = 0; j < C::NI; ++j) { HPFG16_MFMA3(acc[m][j], ah, al, bh[j], bl[j]) }
+      for (int j = 0; j < C::NI; ++j) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[m][j], bh[j], bl[j], ah, al) }
     }
   }
   f32x4 s1[C::NI], s2[C::NI];

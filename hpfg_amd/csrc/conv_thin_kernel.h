@@ -191,11 +191,8 @@ __global__ __launch_bounds__(64 * NW, WGS) void conv_thin_kernel(HpfgConvArgs p,
       for (int m = 0; m < MI; ++m)
 #pragma unroll
         for (int j = 0; j < CO; ++j) {
-          if (G::BREG) {
-            HPFG16_MFMA3(acc[m][j], ah[m], al[m], pbh[G::BREG ? ks : 0][j], pbl[G::BREG ? ks : 0][j])
-          } else {
-            HPFG16_MFMA3(acc[m][j], ah[m], al[m], bh[j], bl[j])
-          }
+          if (G::BREG) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[m][j], pbh[G::BREG ? ks : 0][j], pbl[G::BREG ? ks : 0][j], ah[m], al[m]) }
+          else { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[m][j], bh[j], bl[j], ah[m], al[m]) }
         }
     }
     // ---- epilogue: acc holds D[channel = 4 (lane >> 4) + r][pixel = lane & 15] -> one 16-byte store per lane and tile; BatchNorm sums

@@ -311,11 +311,8 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
         for (int m = 0; m < MI; ++m)
 #pragma unroll
           for (int j = 0; j < CI; ++j) {
-            if (G::BREG) {
-              HPFG16_MFMA3(acc[m][j], ah[m], al[m], pbh[G::BREG ? ks : 0][j], pbl[G::BREG ? ks : 0][j])
-            } else {
-              HPFG16_MFMA3(acc[m][j], ah[m], al[m], bh[j], bl[j])
-            }
+            if (G::BREG) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[m][j], pbh[G::BREG ? ks : 0][j], pbl[G::BREG ? ks : 0][j], ah[m], al[m]) }
+            else { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[m][j], bh[j], bl[j], ah[m], al[m]) }
           }
       }
     }
@@ -372,9 +369,7 @@ __global__ __launch_bounds__(64 * NW, WGS) void fused_bwd_kernel(HpfgFusedBwdArg
           const int ky = tap / 3, kx = tap - 3 * ky;
           const unsigned char* dp = Dj + ((2 * ks - ky + 2) * RS + (2 - kx)) * 32;
           const bf16x8 gh = tr_read8(dp, dp + RS * 32), gl_ = tr_read8(dp + DPL, dp + DPL + RS * 32);
-          accw[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gh, accw[a][t], 0, 0, 0);
-          accw[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gl_, accw[a][t], 0, 0, 0);
-          accw[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, gh, accw[a][t], 0, 0, 0);
+          { HPFG_MFMA3(LO_OF_SECOND_THEN_FIRST, accw[a][t], ah, al, gh, gl_) }
         }
       }
     }

@@ -9,7 +9,7 @@
 //
 // Workgroup = 256 threads = 4 waves, 64 x 64 output tile (each wave 32 x 32 = 2 x 2 MFMA tiles), K in chunks of 16 through LDS.
 // LDS images are k-major with a row stride of 80 floats: the four k rows one MFMA operand read touches start 16 banks apart.
-#include "common.h"
+#include "bf16x3.h"
 
 namespace {
 
@@ -216,23 +216,10 @@ extern "C" int hpfg_relu_bwd(float* dy, const float* y, long n, void* stream) {
 //   Global loads of chunk c+1 are in flight (registers) while chunk c multiplies.
 namespace {
 
-typedef __bf16 g_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 g_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 g_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float g_f32x2 __attribute__((ext_vector_type(2)));
+using namespace hpfg_bf16x3;
 
 constexpr int BM = 128, BK = 32, ROWB = 80;               // bytes per LDS row (64 B of bf16 + 16 B pad)
 constexpr int PLANE_B = BM * ROWB;                        // one hi or lo plane of one operand
-
-__device__ __forceinline__ void split4(const f32x4& v, g_bf16x4& hi, g_bf16x4& lo) {
-  const g_bf16x2 h0 = __builtin_convertvector(g_f32x2{v[0], v[1]}, g_bf16x2), h1 = __builtin_convertvector(g_f32x2{v[2], v[3]}, g_bf16x2);
-  const uint32_t w0 = __builtin_bit_cast(uint32_t, h0), w1 = __builtin_bit_cast(uint32_t, h1);
-  const g_f32x2 f0 = {__builtin_bit_cast(float, w0 << 16), __builtin_bit_cast(float, w0 & 0xFFFF0000u)};
-  const g_f32x2 f1 = {__builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xFFFF0000u)};
-  const g_bf16x2 l0 = __builtin_convertvector(g_f32x2{v[0], v[1]} - f0, g_bf16x2), l1 = __builtin_convertvector(g_f32x2{v[2], v[3]} - f1, g_bf16x2);
-  hi = g_bf16x4{h0[0], h0[1], h1[0], h1[1]};
-  lo = g_bf16x4{l0[0], l0[1], l1[0], l1[1]};
-}
 
 // One operand tile: `rows` index m (or n), element (row, k) at base[row * srow + k * sk]; exactly one of srow / sk is 1.
 struct OpTile {
@@ -262,25 +249,21 @@ constexpr int TRS2 = 288;       // row-fast operands: LDS image [32 k][128 rows]
 __device__ __forceinline__ void tile_store(const OpTile& o, unsigned char* lds, int tid, const f32x4 (&r)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    g_bf16x4 hi, lo;
+    bf16x4 hi, lo;
     split4(r[i], hi, lo);
     // k-fast: [row][k] image, the fragment is a plain 16-byte read.  row-fast (the contraction index is the operand's slow index, e.g. W in
     // dX = dY W): stored as it lies in memory, [k][row], and read through ds_read_b64_tr_b16 -- no scattered 2-byte stores.
     unsigned char* p = o.sk == 1 ? lds + ((tid >> 3) + 32 * i) * ROWB + 8 * (tid & 7) : lds + ((tid >> 5) + 8 * i) * TRS2 + 8 * (tid & 31);
-    *reinterpret_cast<g_bf16x4*>(p) = hi;
-    *reinterpret_cast<g_bf16x4*>(p + PLANE_B) = lo;
+    *reinterpret_cast<bf16x4*>(p) = hi;
+    *reinterpret_cast<bf16x4*>(p + PLANE_B) = lo;
   }
 }
 
-typedef short g2_s16x4 __attribute__((ext_vector_type(4)));
-typedef short g2_s16x8 __attribute__((ext_vector_type(8)));
 // fragment (16 rows starting at row0, this lane's 8 k values) of an operand image, either layout
-__device__ __forceinline__ g_bf16x8 op_frag(const unsigned char* plane, bool tr, int row0, int lane) {
-  if (!tr) return *reinterpret_cast<const g_bf16x8*>(plane + (row0 + (lane & 15)) * ROWB + (lane >> 4) * 16);
+__device__ __forceinline__ bf16x8 op_frag(const unsigned char* plane, bool tr, int row0, int lane) {
+  if (!tr) return *reinterpret_cast<const bf16x8*>(plane + (row0 + (lane & 15)) * ROWB + (lane >> 4) * 16);
   const unsigned char* p = plane + (8 * (lane >> 4) + ((lane & 15) >> 2)) * TRS2 + (row0 + 4 * (lane & 3)) * 2;
-  const g2_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g2_s16x4 __attribute__((address_space(3)))*)(p));
-  const g2_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g2_s16x4 __attribute__((address_space(3)))*)(p + 4 * TRS2));
-  return __builtin_bit_cast(g_bf16x8, (g2_s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}));
+  return tr_read8(p, p + 4 * TRS2);
 }
 
 struct Gemm16Args {
@@ -323,7 +306,7 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(Gemm16Args p, int kper
       tile_load(p.a, m0, k0 + BK, tid, ra);
       tile_load(p.b, n0, k0 + BK, tid, rb);
     }
-    g_bf16x8 bh[4], bl[4];
+    bf16x8 bh[4], bl[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       bh[j] = op_frag(ldsB, btr, wn + 16 * j, lane);
@@ -331,14 +314,10 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(Gemm16Args p, int kper
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const g_bf16x8 ah = op_frag(ldsA, atr, wm + 16 * i, lane);
-      const g_bf16x8 al = op_frag(ldsA + PLANE_B, atr, wm + 16 * i, lane);
+      const bf16x8 ah = op_frag(ldsA, atr, wm + 16 * i, lane);
+      const bf16x8 al = op_frag(ldsA + PLANE_B, atr, wm + 16 * i, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al, acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < 4; ++j) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[i][j], bh[j], bl[j], ah, al) }
     }
   }
   // D[n = (lane >> 4) * 4 + r][m = lane & 15]
@@ -436,16 +415,11 @@ extern "C" int hpfg_gemm_bf16x3_splitk(const float* A, long sam, long sak, const
 //   Workgroup = 256 threads, 64 (n) x 64 (k) output tile, 32 rows per step; wave w owns n-range (w & 1) * 32, k-range (w >> 1) * 32.
 namespace {
 
-typedef short g_s16x4 __attribute__((ext_vector_type(4)));
-typedef short g_s16x8 __attribute__((ext_vector_type(8)));
 constexpr int TR = 32, TT = 64, TRS = 144;            // rows per step, tile edge, LDS row stride in bytes (128 B of bf16 + 16 B: conflict-free tr reads)
 constexpr int TPLANE = TR * TRS;
 
-__device__ __forceinline__ g_bf16x8 tn_frag(const unsigned char* p) {      // p: this lane's address in the first 4-row block; the second is 4 rows below
-  const g_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g_s16x4 __attribute__((address_space(3)))*)(p));
-  const g_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((g_s16x4 __attribute__((address_space(3)))*)(p + 4 * TRS));
-  return __builtin_bit_cast(g_bf16x8, (g_s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}));
-}
+// p: this lane's address in the first 4-row block; the second is 4 rows below
+__device__ __forceinline__ bf16x8 tn_frag(const unsigned char* p) { return tr_read8(p, p + 4 * TRS); }
 
 // rows [r0, r0 + 32) x columns [c0, c0 + 64) of M ([R][C], leading dimension ld) -> hi / lo planes [32][64] bf16 (row stride TRS)
 template <bool ALIGNED>
@@ -470,11 +444,11 @@ __device__ __forceinline__ void tn_load(const float* __restrict__ Mx, long ld, l
 __device__ __forceinline__ void tn_store(unsigned char* lds, int tid, const f32x4 (&v)[2]) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    g_bf16x4 hi, lo;
+    bf16x4 hi, lo;
     split4(v[i], hi, lo);
     unsigned char* p = lds + ((tid >> 4) + 16 * i) * TRS + 8 * (tid & 15);
-    *reinterpret_cast<g_bf16x4*>(p) = hi;
-    *reinterpret_cast<g_bf16x4*>(p + TPLANE) = lo;
+    *reinterpret_cast<bf16x4*>(p) = hi;
+    *reinterpret_cast<bf16x4*>(p + TPLANE) = lo;
   }
 }
 
@@ -512,7 +486,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16x3_kernel(const float* __rest
       tn_load<ALIGNED>(dy, ldy, rb + TR, r1, n0, N, tid, va);
       tn_load<ALIGNED>(x, ldx, rb + TR, r1, k0, K, tid, vb);
     }
-    g_bf16x8 ah[2], al[2], bh[2], bl[2];
+    bf16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       ah[i] = tn_frag(ldsA + fr + (wn + 16 * i) * 2);
@@ -523,11 +497,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16x3_kernel(const float* __rest
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {      // D[row = k][col = n]: a lane ends up with 4 consecutive k of one n
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < 2; ++j) { HPFG_MFMA3(LO_OF_FIRST_THEN_SECOND, acc[i][j], bh[j], bl[j], ah[i], al[i]) }      // D[row = k][col = n]: 4 consecutive k of one n per lane
   }
   float* o = part + (long)blockIdx.z * part_stride;
   if (do_db) {          // 16 row-threads share a column quad: fixed-order sum through LDS; db partial sits behind the N*K weight entries

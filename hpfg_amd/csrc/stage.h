@@ -1,8 +1,10 @@
 // Staging code shared by the four split-bf16 kernel families -- the chunked 3x3 / 1x1 kernels (conv_bf16_kernel.h), the whole-tile forward
 // kernel (conv_thin_kernel.h), the fused dgrad + wgrad kernel (fused_bwd_kernel.h) and the weight gradient (wgrad_bf16_kernel.h).  Each phase
-// below has ONE definition; the kernels differ in the template constants and arguments they pass, never by a branch in here:
-//   * per piece: raw loads of an 8-channel piece of a virtual activation (issue_piece), the producer chain (finish_piece), the bf16 hi / lo
-//     split (split8, split_piece) -- all four families;
+// below has ONE definition; the kernels differ in the template constants and arguments they pass, never by a branch in here.  The arithmetic
+// underneath -- the vector types, the hi / lo split (split8), the transposing LDS read of the kernels that contract over pixels (tr_read8:
+// fused, weight gradient) and the three-issue product (HPFG_MFMA3) -- is bf16x3.h's, shared with the GEMM and attention kernels:
+//   * per piece: raw loads of an 8-channel piece of a virtual activation (issue_piece), the producer chain (finish_piece), its hi / lo
+//     fragments (split_piece) -- all four families;
 //   * per-channel source tables: LDS rows filled once per launch (fill_tables_lds; row stride and row length are the caller's) and read
 //     back into a Tab (load_tables_lds<KIND, STRIDE>) -- all four families;
 //   * the upsampled half of a concat source through an LDS patch: geometry (UpPatch), first source row / column (up_base), the patch
@@ -10,7 +12,6 @@
 //     all four families; the blend of an output piece's four taps from the patch (up_blend) -- chunked, weight gradient.  Patch channel
 //     stride and width are template constants, the halo and the validity mask are the caller's arguments;
 //   * the XCD-contiguous tile walk (tile_walk) -- all four families; the number of XCD groups is the caller's (see there);
-//   * the transposing LDS read of the kernels that contract over pixels (tr_read8) -- fused, weight gradient;
 //   * the in-kernel time stamps of the diagnostics build (HPFG_TR, HPFG_TR_REAL) -- chunked, fused, weight gradient.
 // The whole-tile layout that the thin and the fused kernel share on top of this is tile16.h.
 // Deliberate exceptions (a phase stays a family's own text where the shared form would need a branch on its caller, or changes a result):
@@ -21,46 +22,14 @@
 //     do not change with the work item), not the LDS rows;
 //   * weight gradient, SPLIT16 operands: their issue is an address select and their staging a copy (wgrad_bf16_kernel.h), no piece chain.
 #pragma once
-#include "common.h"
+#include "bf16x3.h"
 
 namespace hpfg_stage {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// x = hi + lo with hi = bf16(x) (round to nearest even), lo = bf16(x - hi): pairs go through v_cvt_pk_bf16_f32, and the packed
-// hi word is widened back with one shift / one mask per pair.
-__device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
-  uint32_t hw[4], lw[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float x0 = k < 2 ? a[2 * k] : b[2 * k - 4], x1 = k < 2 ? a[2 * k + 1] : b[2 * k - 3];
-    const bf16x2 h = __builtin_convertvector(f32x2{x0, x1}, bf16x2);
-    const uint32_t w = __builtin_bit_cast(uint32_t, h);
-    const f32x2 hf = {__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xFFFF0000u)};
-    const bf16x2 l = __builtin_convertvector(f32x2{x0, x1} - hf, bf16x2);
-    hw[k] = w;
-    lw[k] = __builtin_bit_cast(uint32_t, l);
-  }
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  hi = __builtin_bit_cast(bf16x8, (u32x4{hw[0], hw[1], hw[2], hw[3]}));
-  lo = __builtin_bit_cast(bf16x8, (u32x4{lw[0], lw[1], lw[2], lw[3]}));
-}
+using namespace hpfg_bf16x3;
 
 __device__ __forceinline__ f32x4 ld4(const float* base, int off) { return *reinterpret_cast<const f32x4*>(base + off); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }   // v_med3_i32
-
-// ds_read_b64_tr_b16 twice: row0 / row1 are this lane's addresses inside two 4-pixel blocks of a pixel-major [pixel][16 ch] bf16 image
-// (wgrad_bf16_kernel.h); the result is 8 k-values (pixels) of this lane's channel
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ bf16x8 tr_read8(const unsigned char* row0, const unsigned char* row1) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(row0));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(row1));
-  return __builtin_bit_cast(bf16x8, (s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}));
-}
 
 // Diagnostics build only (make TRACE=1 -> libhpfg_hip_trace.so, tools/trace_conv.py, tools/trace_fused.py): with math bit 0x2000 one thread
 // of every workgroup writes (id << 56 | s_memtime) stamps to the kernel's own u64 buffer tr_buf (256 per workgroup; the kernel says where).

@@ -368,10 +368,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
                 cl[kx] = al;
               }
             }
-            const int t = ky * 3 + kx;
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gh, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gl, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, gh, acc[t], 0, 0, 0);
+            { HPFG_MFMA3(LO_OF_SECOND_THEN_FIRST, acc[ky * 3 + kx], ah, al, gh, gl) }
           }
         }
       }
@@ -389,9 +386,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_bf16x3_kernel(HpfgWgradArgs p, 
           const unsigned char* a = ldsA + wi * 2 * A_PLANE + ((r0 + ky) * WP + xoff + kx) * 32 + pp * 8;
           const bf16x8 ah = tr_read8(a, a + WP * 32);
           const bf16x8 al = tr_read8(a + A_PLANE, a + A_PLANE + WP * 32);
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gh, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, gl, acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, gh, acc[t], 0, 0, 0);
+          { HPFG_MFMA3(LO_OF_SECOND_THEN_FIRST, acc[t], ah, al, gh, gl) }
         }
       }
     }
