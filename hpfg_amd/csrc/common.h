@@ -257,7 +257,13 @@ __device__ static inline f32x4 act_load4(const HpfgAct& s, const ActCtx& cx, int
   switch (s.mode) {
     case HPFG_ACT_PLAIN: {
       const float* p = s.z + ((long)(n * s.Hs + y) * s.Ws + x) * s.pstride + c;
-      v = *reinterpret_cast<const f32x4*>(p);
+      if (c + 4 <= s.C) {
+        v = *reinterpret_cast<const f32x4*>(p);
+      } else {      // the source ends inside this quad: lane by lane, so that the next pixel (or what follows the tensor) is not read for channels >= C
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (c + j < s.C) v[j] = p[j];
+      }
       break;
     }
     case HPFG_ACT_STRIDED: {
@@ -438,6 +444,22 @@ __device__ __forceinline__ float hpfg_own_vgpr(float x) {
 #else
 #define HPFG_NO_PK_F32
 #endif
+
+// "Channels >= s.C read as zero" for the staged loaders (stage.h issue_piece), whose PLAIN branch requests whole quads a tile ahead and
+// cannot mask them before they arrive: with C % 4 != 0 the last quad of a pixel would take its upper lanes from the next pixel -- behind the
+// last pixel from whatever follows the tensor -- and a NaN or Inf there survives the zero weight rows it meets (0 * NaN).  The entry points
+// that hand a source to those kernels (hpfg_conv_fwd, hpfg_wgrad, the dZ side of hpfg_fused_bwd) pass it through here: a PLAIN source
+// that ends inside a quad is read as the STRIDED source over the same tensor, lane by lane, which is what engine.py describes for such
+// channel counts anyway.  Host side only: the kernels' code does not change, and no launch with C % 4 == 0 takes another path.
+// tests/test_gpu_tile_edges.py, group D, holds every route to it.
+static inline void hpfg_plain_by_lane(HpfgAct& a) {
+  if (a.mode != HPFG_ACT_PLAIN || (a.C & 3) == 0) return;
+  a.mode = HPFG_ACT_STRIDED;
+  a.sn = a.Hs * a.Ws * a.pstride;
+  a.sc = 1;
+  a.sy = a.Ws * a.pstride;
+  a.sx = a.pstride;
+}
 
 static inline int hpfg_kind_of(const HpfgAct& a0, const HpfgAct& a1) {
   if (a1.mode == HPFG_ACT_UP2X && a0.mode == HPFG_ACT_BNACT) return HPFG_KIND_CAT;

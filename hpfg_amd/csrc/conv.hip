@@ -282,6 +282,12 @@ extern "C" int hpfg_conv_stat_rows(const HpfgConvArgs* a) {
 
 static int conv_fwd_impl(const HpfgConvArgs* a, void* stream, int* rows_only) {
   HPFG_ARG_CHECK(a && a->wpk && a->out, "conv_fwd: null pointer");
+  HpfgConvArgs by_lane;
+  if (a->a0.mode == HPFG_ACT_PLAIN && (a->a0.C & 3)) {      // a PLAIN source that ends inside a quad: common.h hpfg_plain_by_lane
+    by_lane = *a;
+    hpfg_plain_by_lane(by_lane.a0);
+    a = &by_lane;
+  }
   HPFG_ARG_CHECK(a->taps == 9 || a->taps == 1, "conv_fwd: taps must be 1 or 9 (got %d)", a->taps);
   HPFG_ARG_CHECK(a->CoutPad % 16 == 0 && a->Cout <= a->CoutPad && a->Cout > 0, "conv_fwd: bad Cout %d / pad %d", a->Cout, a->CoutPad);
   HPFG_ARG_CHECK(a->N > 0 && a->H > 0 && a->W > 0 && a->N < 65536, "conv_fwd: bad N/H/W");

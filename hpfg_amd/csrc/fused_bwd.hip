@@ -75,6 +75,12 @@ extern "C" int hpfg_fused_bwd_grid(const HpfgFusedBwdArgs* a) {
 extern "C" int hpfg_fused_bwd(const HpfgFusedBwdArgs* a, void* stream) {
   const int c = check(a);
   if (c < 0) return -1;
+  HpfgFusedBwdArgs by_lane;
+  if (a->d.a0.mode == HPFG_ACT_PLAIN && (a->d.a0.C & 3)) {      // a PLAIN gradient that ends inside a quad: common.h hpfg_plain_by_lane
+    by_lane = *a;
+    hpfg_plain_by_lane(by_lane.d.a0);
+    a = &by_lane;
+  }
   HPFG_ARG_CHECK(c == 0, "fused_bwd: 3x3 bf16x3 layers with H, W multiples of 16, CinPad <= 64 and CoutPad <= 32 only");
   const HpfgConvArgs& d = a->d;
   const bool wonly = !d.out;      // no dX wanted: weight gradient only (first layer)

@@ -230,7 +230,7 @@ __device__ __forceinline__ void issue_piece(RawPiece<KIND>& rp, const HpfgAct& a
     if (a.mode == HPFG_ACT_STRIDED) {
       raw[0] = act_load4_mode<HPFG_ACT_STRIDED>(a, cx0, n, gy, gx, c0);
       raw[1] = act_load4_mode<HPFG_ACT_STRIDED>(a, cx0, n, gy, gx, c0 + 4);
-    } else {
+    } else {      // whole quads: C % 4 == 0 here -- a PLAIN source that ends inside a quad arrives as STRIDED (common.h hpfg_plain_by_lane)
       const int off = ((n * a.Hs + gy) * a.Ws + gx) * a.pstride + c0;
       raw[0] = ld4(a.z, off);
       raw[1] = f32x4{0.f, 0.f, 0.f, 0.f};

@@ -166,6 +166,13 @@ extern "C" long hpfg_wgrad_slab_floats(int N, int H, int W, int CinPad, int Cout
 
 extern "C" int hpfg_wgrad(const HpfgWgradArgs* a, void* stream) {
   HPFG_ARG_CHECK(a && a->slab && a->dw_oihw, "wgrad: null pointer");
+  HpfgWgradArgs by_lane;
+  if ((a->a0.mode == HPFG_ACT_PLAIN && (a->a0.C & 3)) || (a->g.mode == HPFG_ACT_PLAIN && (a->g.C & 3))) {
+    by_lane = *a;      // a PLAIN source that ends inside a quad (common.h hpfg_plain_by_lane; here the strays would only land in padded slab entries,
+    hpfg_plain_by_lane(by_lane.a0);      // but the last pixel's quad would still be read from behind the tensor)
+    hpfg_plain_by_lane(by_lane.g);
+    a = &by_lane;
+  }
   HPFG_ARG_CHECK(a->taps == 9 || a->taps == 1, "wgrad: taps must be 1 or 9");
   HPFG_ARG_CHECK(a->CinPad % 16 == 0 && a->CoutPad % 16 == 0 && a->Cin <= a->CinPad && a->Cout <= a->CoutPad, "wgrad: bad channel padding");
   HPFG_ARG_CHECK(a->S >= 1, "wgrad: S < 1");

@@ -23,7 +23,7 @@ int hpfg_wgrad16_launch_split(const HpfgWgradArgs& a, int akind, hipStream_t st)
     }
   } else if (akind == HPFG_KIND_SPLIT) {
     if (a.g.mode == HPFG_ACT_DZ) return launch_wgrad16<HPFG_KIND_SPLIT, HPFG_KIND_DZ>(a, st);
-    if (a.g.mode == HPFG_ACT_PLAIN) return launch_wgrad16<HPFG_KIND_SPLIT, HPFG_KIND_PLAIN>(a, st);
+    if (a.g.mode == HPFG_ACT_PLAIN || a.g.mode == HPFG_ACT_STRIDED) return launch_wgrad16<HPFG_KIND_SPLIT, HPFG_KIND_PLAIN>(a, st);
   }
   hpfg_set_error("wgrad(bf16x3): unsupported combination of sources with a SPLIT16 operand (input kind %d, gradient mode %d)", akind, a.g.mode);
   return -1;

@@ -556,8 +556,9 @@ def materialized_within_delta(got, kind, z, tab, u=None, dA=None, p=0.0, seed=0)
 #   3 * 2^-16 * S        each operand is represented to 2^-16 relative (2), the dropped lo*lo term is at most 2^-16 (1)
 #   (T + 2) * 2^-24 * S  the fp32 sum
 #   sum |w| * delta_a    the fp32 rounding of the source chain, per kind as stated above
-def _split_bound(S, T, chain):
-    return 3.0 * 2.0 ** -16 * S + (T + 2) * U24 * S + chain
+def _split_bound(S, T, chain, split=True):
+    """split=False: a kernel that forms its products in exact fp32 FMAs -- the fp32 sum and the chain alone"""
+    return (3.0 * 2.0 ** -16 * S if split else 0.0) + (T + 2) * U24 * S + chain
 
 
 def conv_ref_bound(a, da, w, b):
@@ -584,9 +585,10 @@ def dgrad_ref_bound(g, dg, w):
     return x.grad.permute(0, 2, 3, 1).contiguous(), _split_bound(S, T, chain).permute(0, 2, 3, 1).contiguous()
 
 
-def wgrad_ref_bound(a, da, g, dg, wshape):
+def wgrad_ref_bound(a, da, g, dg, wshape, split=True):
     """a, da [N,H,W,Cin], g, dg [N,H,W,Cout] float64 -> (float64 autograd of F.conv2d w.r.t. its weight, bound), both [Cout,Cin,k,k]; the sum
-    runs over the pixels: T = N * H * W, the chain term |a| dg + da |g| + da dg"""
+    runs over the pixels: T = N * H * W, the chain term |a| dg + da |g| + da dg.  split=False: without the 3 * 2^-16 * S term of the split
+    products (first_wgrad_kernel multiplies in fp32)"""
     from torch.nn import grad as G
     pad = wshape[-1] // 2
     x = nchw(a)
@@ -595,7 +597,7 @@ def wgrad_ref_bound(a, da, g, dg, wshape):
     cw = lambda p_, q_: G.conv2d_weight(nchw(p_), wshape, nchw(q_), padding=pad)
     S = cw(a.abs(), g.abs())
     chain = cw(a.abs(), dg) + cw(da, g.abs()) + cw(da, dg)
-    return wr.grad, _split_bound(S, a.shape[0] * a.shape[1] * a.shape[2], chain)
+    return wr.grad, _split_bound(S, a.shape[0] * a.shape[1] * a.shape[2], chain, split)
 
 
 def f32_conv_ratio(kind, ref, bound, *args):
@@ -625,24 +627,39 @@ def adhoc_weights(cin, cout, taps, seed):
 
 
 @functools.lru_cache(maxsize=None)
-def conv_source(kind, seed, N, H, W, C_, p=0.0):
+def conv_source(kind, seed, N, H, W, C_, p=0.0, hot=None):
     """One virtual source of a conv at N x H x W with C_ channels, on the CPU: its raw float32 tensors (unit-scale data, hand-made table),
     the float64 restatement `v` and its `delta`.  kind: plain | bnact | pool (raw tensors at 2H x 2W) | cat ([bnact C/2 | up2x C/2], the
-    upsampled half at H/2 x W/2) | dz.  The LeakyReLU guard of lrelu_slope holds for the seeds in use.  Computed once; read-only."""
+    upsampled half at H/2 x W/2) | dz.  hot = (n, y0, x0, A): the raw tensors of the 16 x 16 tile at (y0, x0) of image n are A times as large
+    (the walk cases of tests/test_gpu_tile_edges.py).  The LeakyReLU guard of lrelu_slope holds for the seeds in use.  Computed once; read-only."""
     g = torch.Generator().manual_seed(seed)
     rn = lambda *s: torch.randn(*s, generator=g) * 2 + 0.5
+
+    def heat(t, up=1.0):
+        if hot is not None:
+            n, y0, x0, A = hot
+            t[n, int(y0 * up):int((y0 + 16) * up), int(x0 * up):int((x0 + 16) * up)] *= A
+        return t
+
+    def untie(z, tab):
+        """among millions of elements a few sit on a LeakyReLU tie (the condition of lrelu_slope): those move by 1/4 (none in the small cases)"""
+        zs, sh = z.double() * tab[L.BN_SCALE].double(), tab[L.BN_SHIFT].double()
+        z[(zs + sh).abs() <= 2.0 ** -22 * torch.maximum(zs.abs(), sh.abs().expand_as(zs))] += 0.25
+        return z
+
     s = dict(kind=kind, C=C_, p=p, dseed=1000 + seed)
     if kind == "plain":
-        s["z"] = rn(N, H, W, C_)
+        s["z"] = heat(rn(N, H, W, C_))
         s["v"], s["d"] = s["z"].double(), torch.zeros(N, H, W, C_, dtype=torch.float64)
         return s
     if kind == "dz":
-        s["z"], s["dA"], s["tab"] = rn(N, H, W, C_), torch.randn(N, H, W, C_, generator=g), bn_table(C_, seed + 11)
+        s["z"], s["dA"], s["tab"] = heat(rn(N, H, W, C_)), heat(torch.randn(N, H, W, C_, generator=g)), bn_table(C_, seed + 11)
+        untie(s["z"], s["tab"])
         s["v"], s["d"] = dz_f64(s["z"], s["dA"], s["tab"], p, s["dseed"])
         return s
     ca = C_ // 2 if kind == "cat" else C_
     up = 2 if kind == "pool" else 1
-    s["z"], s["tab"] = rn(N, up * H, up * W, ca), bn_table(ca, seed + 3)
+    s["z"], s["tab"] = untie(heat(rn(N, up * H, up * W, ca), up), bn_table(ca, seed + 3)), bn_table(ca, seed + 3)
     sc, sh = s["tab"][L.BN_SCALE], s["tab"][L.BN_SHIFT]
     lrelu_slope(s["z"].double(), sc.double(), sh.double())          # the guard
     if kind == "bnact":
@@ -650,7 +667,7 @@ def conv_source(kind, seed, N, H, W, C_, p=0.0):
     elif kind == "pool":
         s["v"], s["d"] = pool_f64(s["z"], sc, sh)
     else:
-        s["u"] = rn(N, H // 2, W // 2, C_ - ca)
+        s["u"] = heat(rn(N, H // 2, W // 2, C_ - ca), 0.5)
         s["v"], s["d"] = cat_f64(s["z"], sc, sh, s["u"])
     return s
 
@@ -703,6 +720,255 @@ def pool_epilogue_source(seed, N, H, W, C_):
     a, mag = _act64(s["z"], s["tab"][L.BN_SCALE], s["tab"][L.BN_SHIFT])
     s["first"] = pool_argmax(a, 3.0 * U24 * mag)
     return s
+
+
+# ---- NaN-filled layouts of the kernel-by-kernel conv tests (tests/test_gpu_conv_sources.py, tests/test_gpu_tile_edges.py) ----------------
+NAN = float("nan")
+PADC, COFF = 12, 4          # raw tensors: channel offset COFF inside a buffer of C + PADC floats per pixel
+APAD, AOFF = 20, 8          # the dA tensor of a dz source (aux_pstride differs from pstride)
+TPAD, TOFF = 16, 8          # tables: column offset TOFF (bn_coff) inside rows of C + TPAD
+OPAD, OOFF = 12, 4          # outputs
+O2PAD, O2OFF = 20, 8        # second output (out2)
+
+
+def wide(t, pad=PADC, coff=COFF, dev="cuda:0"):
+    """CPU tensor [..., C] -> (NaN-filled device buffer [..., C + pad] with t at channel offset coff, address of its first interior element)"""
+    c = t.shape[-1]
+    buf = torch.full(tuple(t.shape[:-1]) + (c + pad,), NAN, device=dev)
+    buf[..., coff:coff + c] = t.to(dev)
+    return buf, buf.data_ptr() + 4 * coff
+
+
+def interior(buf, c, coff):
+    """(interior [..., c], True when every element around it is still NaN)"""
+    mask = torch.ones(buf.shape[-1], dtype=torch.bool, device=buf.device)
+    mask[coff:coff + c] = False
+    return buf[..., coff:coff + c], bool(torch.isnan(buf[..., mask]).all())
+
+
+def layout_acts(kind, C_, H, W, p=0.0, dseed=0, ptr=256):
+    """(a0, a1 or None) of a source of `kind` with C_ channels feeding a conv at H x W in the layout of device_source: every field but the
+    addresses, which are `ptr` (enough for the host-side grid queries hpfg_conv_stat_rows / hpfg_fused_bwd_grid)"""
+    ca = C_ // 2 if kind == "cat" else C_
+    up = 2 if kind == "pool" else 1
+    a = L.Act()
+    a.z, a.C, a.Hs, a.Ws, a.pstride = ptr, ca, up * H, up * W, ca + PADC
+    if kind == "plain":
+        a.mode = L.ACT_PLAIN
+        return a, None
+    a.bn, a.bn_stride, a.bn_coff = ptr, ca + TPAD, TOFF
+    a.drop_p, a.drop_seed = p, dseed
+    a.mode = {"bnact": L.ACT_BNACT, "pool": L.ACT_BNACT_POOL, "cat": L.ACT_BNACT, "dz": L.ACT_DZ}[kind]
+    a1 = None
+    if kind == "dz":
+        a.aux, a.aux_pstride = ptr, ca + APAD
+    if kind == "cat":
+        a1 = L.Act()
+        a1.z, a1.mode, a1.C, a1.Hs, a1.Ws, a1.pstride = ptr, L.ACT_UP2X, C_ - ca, H // 2, W // 2, C_ - ca + PADC
+    return a, a1
+
+
+def device_source(s, H, W, dev="cuda:0"):
+    """conv_source dict -> (a0, a1 or None, tensors to keep alive) on the device, every tensor and table inside a wider NaN-filled one"""
+    kind, C_, keep = s["kind"], s["C"], []
+    a = L.Act()
+    zb, a.z = wide(s["z"], dev=dev)
+    keep.append(zb)
+    ca = s["z"].shape[-1]
+    a.C, a.Hs, a.Ws, a.pstride = ca, s["z"].shape[1], s["z"].shape[2], ca + PADC
+    if kind == "plain":
+        a.mode = L.ACT_PLAIN
+        return a, None, keep
+    tb = torch.full((L.BN_ROWS, ca + TPAD), NAN, device=dev)
+    tb[:, TOFF:TOFF + ca] = s["tab"].to(dev)
+    keep.append(tb)
+    a.bn, a.bn_stride, a.bn_coff = L.ptr(tb), ca + TPAD, TOFF
+    a.drop_p, a.drop_seed = s["p"], s["dseed"]
+    a.mode = {"bnact": L.ACT_BNACT, "pool": L.ACT_BNACT_POOL, "cat": L.ACT_BNACT, "dz": L.ACT_DZ}[kind]
+    a1 = None
+    if kind == "dz":
+        ab, a.aux = wide(s["dA"], APAD, AOFF, dev)
+        a.aux_pstride = ca + APAD
+        keep.append(ab)
+    if kind == "cat":
+        a1 = L.Act()
+        ub, a1.z = wide(s["u"], dev=dev)
+        keep.append(ub)
+        a1.mode, a1.C, a1.Hs, a1.Ws, a1.pstride = L.ACT_UP2X, C_ - ca, s["u"].shape[1], s["u"].shape[2], C_ - ca + PADC
+    return a, a1, keep
+
+
+def as_strided_act(a):
+    """a PLAIN source over [N, Hs, Ws, pstride] read through strides instead (what the engine does when C % 4 != 0: per-lane loads)"""
+    a.mode = L.ACT_STRIDED
+    a.sn, a.sc, a.sy, a.sx = a.Hs * a.Ws * a.pstride, 1, a.Ws * a.pstride, a.pstride
+    return a
+
+
+# ---- the whole-tile kernels (tests/test_gpu_tile_edges.py): conv_thin_kernel, fused_bwd_kernel, first_wgrad_kernel -----------------------
+# Tile-count edges, per instantiation: one 16 x 16 tile (seven of the eight workgroups own none), fewer tiles than workgroups with
+# tiles_x != tiles_y, and the walk case -- more tiles than the launch has workgroups, so the tile loop of a workgroup runs two or three times
+# (prefetch of the next tile, the drain of the last, sums and weight-gradient accumulators carried across tiles).
+TILE_EDGES = {"one": (1, 16, 16), "few": (1, 32, 48)}
+WALK_HW = (96, 160)                       # 6 x 10 tiles an image
+SWEEP = (2, 32, 48)                       # the channel / dropout sweeps: 12 tiles on 16 workgroups, some with two tiles, some with none
+HOT = (32, 48, 8.0)                       # walk cases: the tile at (y0, x0) of the middle image carries 8 x the amplitude (see walk_hot)
+OLD_KERNEL = 0x4000                       # any flag bit in `math` keeps a launch on the chunked conv_bf16x3_kernel
+
+
+def walk_hot(edge, N):
+    """The weight-gradient bound grows with (N H W + 2) * 2^-24 * sum|a||g| -- at the 140 to 200 thousand pixels a walk needs, a missing tile
+    of unit-scale data (256 pixels) is far inside it.  One interior tile of the walk cases therefore carries 8 x the amplitude in both
+    operands (64 x in the products), which puts a weight gradient without that tile outside the bound (tests/test_host_logic.py)."""
+    return (N // 2,) + HOT if edge == "walk" else None
+
+
+def walk_conditions(nwork, rows, tiles_x, tiles_y, wgs):
+    """the tile loop of a workgroup runs at least twice (three times with one workgroup per CU), unevenly, on a non-square grid of tiles"""
+    return 0 < rows < nwork and -(-nwork // rows) >= (3 if wgs == 1 else 2) and nwork % rows != 0 and tiles_x != tiles_y
+
+
+# conv_thin_kernel<CI, CO, kind>: source kind -> (layer cin, layer cout of the edge cases, workgroups per CU, images of the walk case)
+THIN_INST = {"bnact": (16, 16, 3, 13), "pool": (16, 32, 1, 9), "cat": (32, 16, 2, 10), "dz": (64, 32, 1, 9)}
+# thin case: source kind, p, N, H, W, layer cin, layer cout, edge.  kind dz = the dgrad of the 64 -> 32 layer (source of 32 channels, 64 out)
+THIN_CASES = ([("bnact", p, *SWEEP, 16, co, "") for co in (4, 8, 12, 16) for p in (0.0, 0.3)] +
+              [("pool", 0.0, *SWEEP, 16, co, "") for co in (20, 24, 32)] + [("cat", 0.0, *SWEEP, 32, co, "") for co in (4, 16)] +
+              [("dz", p, *SWEEP, 64, 32, "") for p in (0.0, 0.3)] +
+              [(k, 0.0, *TILE_EDGES[e], ci, co, e) for k, (ci, co, _, _) in THIN_INST.items() for e in TILE_EDGES] +
+              [(k, 0.0, n, *WALK_HW, ci, co, "walk") for k, (ci, co, _, n) in THIN_INST.items()])
+# fused_bwd_kernel<CI, CO, input kind, dZ kind>: name -> (input kind, dZ kind, cin, cout of the edge cases, workgroups per CU, images of the
+# walk case); `first` = the first layer's weight-gradient-only form (NODG) on an RGB input read through its strides
+FUSED_INST = {"bnact_dz": ("bnact", "dz", 16, 16, 2, 10), "bnact_plain": ("bnact", "plain", 16, 4, 2, 10), "pool_dz": ("pool", "dz", 16, 32, 1, 9),
+              "bnact32_dz": ("bnact", "dz", 32, 32, 1, 9), "cat_dz": ("cat", "dz", 32, 16, 1, 9), "first": ("plain", "dz", 3, 16, 2, 10)}
+# fused case: input kind, p_in, dZ kind, p_out, N, H, W, cin, cout, out_split, edge
+FUSED_CASES = ([("bnact", pi, "dz", po, *SWEEP, 16, 16, 0, "") for pi, po in ((0.0, 0.0), (0.3, 0.0), (0.0, 0.3), (0.3, 0.3))] +
+               [("bnact", 0.0, "dz", 0.0, *SWEEP, 16, 8, 0, "")] +
+               [("bnact", 0.0, "plain", 0.0, *SWEEP, 16, co, 0, "") for co in (2, 3, 4, 5, 9, 13, 16)] +
+               [("pool", 0.0, "dz", 0.3, *SWEEP, 16, co, 0, "") for co in (24, 32)] + [("bnact", 0.3, "dz", 0.0, *SWEEP, 32, co, 0, "") for co in (24, 32)] +
+               [("cat", 0.0, "dz", 0.0, *SWEEP, 32, 8, 16, ""), ("cat", 0.0, "dz", 0.3, *SWEEP, 32, 16, 16, ""), ("cat", 0.0, "dz", 0.0, *SWEEP, 32, 16, 0, "")] +
+               [(ak, 0.0, gk, 0.0, *TILE_EDGES[e], ci, co, 16 if ak == "cat" else 0, e) for ak, gk, ci, co, _, _ in FUSED_INST.values() for e in TILE_EDGES] +
+               [(ak, 0.0, gk, 0.0, n, *WALK_HW, ci, co, 16 if ak == "cat" else 0, "walk") for ak, gk, ci, co, _, n in FUSED_INST.values()])
+# first_wgrad_kernel and the tile form it replaces: N, H, W, cin, p, layout of the STRIDED input (nchw | crop | nhwc3), HPFG_OPT_FIRST_WGRAD.
+# W = 64: one live load of the four a thread requests; W = 512: the parked rows exactly; N H = 784 > 768 rows: the work-item loop runs twice
+FIRST_LAYOUTS = ("nchw", "crop", "nhwc3")
+FIRST_CASES = ([(n, 16, w, 1, p, lay, st) for n, w in ((2, 64), (2, 80), (2, 272), (2, 512), (49, 64)) for p in (0.0, 0.05) for lay in FIRST_LAYOUTS
+                for st in (1, 0)] + [(2, 16, 80, 3, 0.05, "nchw", 1)])      # (RGB: the tile form whatever the option says)
+# the partial-quad contract of PLAIN sources ("channels >= C read as zero"): C, layout (tail: tight [N,H,W,C] with NaN behind the last pixel
+# inside the allocation | wide: NaN between the pixels)
+QUAD_C = (2, 3, 5, 9, 13)
+QUAD_LAYOUTS = ("tail", "wide")
+QUAD_FUSED = [("bnact", 0.0, "plain", 0.0, *SWEEP, 16, c, 0, "") for c in QUAD_C]                 # out_conv through hpfg_fused_bwd (cases of FUSED_CASES)
+QUAD_DGRAD = [("plain", 0.0, 3, 10, 34, 16, c, None, None) for c in QUAD_C]                       # ... and through the chunked kernels at a size that is
+QUAD_WGRAD = [("bnact", 0.0, "plain", 0.0, 3, 10, 34, 16, c, 9) for c in QUAD_C]                  # not 16-aligned (the layouts of DGRAD3_CASES / WGRAD_CASES)
+
+
+@functools.lru_cache(maxsize=None)
+def thin_case(case):
+    """CPU data of a THIN_CASES entry: source, weights, float64 reference and bound of the output, the ratio torch float32 reaches.  Read-only."""
+    kind, p, N, H, W, cin, cout, edge = case
+    seed = case_seed(*case)
+    w, b = adhoc_weights(cin, cout, 9, seed)
+    if kind == "dz":
+        s = conv_source("dz", seed, N, H, W, cout, p, walk_hot(edge, N))
+        ref, bound = dgrad_ref_bound(s["v"], s["d"], w)
+        f32 = f32_conv_ratio("dgrad", ref, bound, s["v"], w)
+    else:
+        s = conv_source(kind, seed, N, H, W, cin, p, walk_hot(edge, N))
+        ref, bound = conv_ref_bound(s["v"], s["d"], w, b)
+        f32 = f32_conv_ratio("conv", ref, bound, s["v"], w, b)
+    return dict(s=s, w=w, b=b, ref=ref, bound=bound, f32=f32, seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def fused_case(case):
+    """CPU data of a FUSED_CASES entry: layer input sa, dZ source sg, weights, (reference, bound, torch-float32 ratio) of dX (None for the
+    first layer, which has none) and of dW.  Read-only."""
+    ak, p_in, gk, p_out, N, H, W, cin, cout, split, edge = case
+    seed = case_seed(*case)
+    hot = walk_hot(edge, N)
+    sa, sg = conv_source(ak, seed, N, H, W, cin, p_in, hot), conv_source(gk, seed + 1, N, H, W, cout, p_out, hot)
+    w, _ = adhoc_weights(cin, cout, 9, seed)
+    out = dict(sa=sa, sg=sg, w=w, seed=seed, dx=None)
+    if cin >= 16:
+        ref, bound = dgrad_ref_bound(sg["v"], sg["d"], w)
+        out["dx"] = (ref, bound, f32_conv_ratio("dgrad", ref, bound, sg["v"], w))
+    ref, bound = wgrad_ref_bound(sa["v"], sa["d"], sg["v"], sg["d"], w.shape)
+    out["dw"] = (ref, bound, f32_conv_ratio("wgrad", ref, bound, sa["v"], sg["v"], w.shape))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def first_case(N, H, W, cin, p):
+    """CPU data of the FIRST_CASES entries at one shape and dropout rate: the network input x (a plain source), the dZ source of the 16
+    output channels, the float64 weight gradient, its bound without the split term (the streaming kernel: exact fp32 products) and with it
+    (the tile form), the torch-float32 ratio against the former.  Read-only."""
+    seed = case_seed("first", N, H, W, cin, p)
+    sx, sg = conv_source("plain", seed, N, H, W, cin), conv_source("dz", seed + 1, N, H, W, 16, p)
+    shape = (16, cin, 3, 3)
+    ref, b_stream = wgrad_ref_bound(sx["v"], sx["d"], sg["v"], sg["d"], shape, split=False)
+    _, b_tile = wgrad_ref_bound(sx["v"], sx["d"], sg["v"], sg["d"], shape)
+    return dict(sx=sx, sg=sg, ref=ref, b_stream=b_stream, b_tile=b_tile, f32=f32_conv_ratio("wgrad", ref, b_stream, sx["v"], sg["v"], shape), seed=seed)
+
+
+def fwd_sums_ratio(part64, out):
+    """rows of (sum z, sum z^2), summed in float64 -> part64 [2][C], against the float64 sums of the launch's own read-back output [.., C]: the
+    fp32 summation bound of tests/test_gpu_bn_acc.py::_fwd_sums_check, (n + 2) * 2^-24 * sum|term|.  -> largest error / bound"""
+    z = out.detach().cpu().double().reshape(-1, out.shape[-1])
+    n = z.shape[0]
+    worst = 0.0
+    for which, term in enumerate((z, z * z)):
+        worst = max(worst, float(((part64[which] - term.sum(0)).abs() / ((n + 2) * U24 * term.abs().sum(0))).max()))
+    return worst
+
+
+def bwd_sums_ratio(part64, g64, z64, tab):
+    """rows of (sum g, sum g xhat), summed in float64 -> part64 [2][C], against float64 sums of g64, z64 [n][C]: the bound of
+    tests/test_gpu_bn_acc.py::_bwd_sums_check -- (n + 2) * 2^-24 * sum|g| and (n + 4) * 2^-24 * rstd * (sum|g z| + |mean| sum|g|), the epilogues
+    form rstd * (sum g z - mean * sum g) in fp32.  -> largest error / bound"""
+    n = g64.shape[0]
+    mean, rstd = tab[L.BN_MEAN].double(), tab[L.BN_RSTD].double()
+    r1 = (part64[0] - g64.sum(0)).abs() / ((n + 2) * U24 * g64.abs().sum(0))
+    r2 = (part64[1] - (g64 * ((z64 - mean) * rstd)).sum(0)).abs() / ((n + 4) * U24 * rstd * ((g64 * z64).abs().sum(0) + mean.abs() * g64.abs().sum(0)))
+    return max(float(r1.max()), float(r2.max()))
+
+
+def thin_args(case, math=L.MATH_BF16X3):
+    """HpfgConvArgs of a THIN_CASES entry in the layout of tests/test_gpu_tile_edges.py, dummy addresses: for hpfg_conv_stat_rows on the host"""
+    kind, p, N, H, W, cin, cout, _ = case
+    dgrad = kind == "dz"
+    ca = L.ConvArgs()
+    a0, a1 = layout_acts(kind, cout if dgrad else cin, H, W, p)
+    ca.a0, ca.a1 = a0, (a1 if a1 is not None else L.Act())
+    oc = cin if dgrad else cout
+    ca.wpk, ca.out, ca.math, ca.taps, ca.N, ca.H, ca.W = 256, 256, math, 9, N, H, W
+    ca.Cout, ca.CoutPad, ca.out_pstride = oc, pad16(oc), oc + OPAD
+    if not dgrad:
+        ca.bias = ca.stat_partials = 256
+    return ca
+
+
+def fused_args(case):
+    """HpfgFusedBwdArgs of a FUSED_CASES entry in the layout of tests/test_gpu_tile_edges.py, dummy addresses: for hpfg_fused_bwd_grid on the
+    host (the grid does not depend on bwd_stats)"""
+    ak, p_in, gk, p_out, N, H, W, cin, cout, split, _ = case
+    fa = L.FusedBwdArgs()
+    xa0, xa1 = layout_acts(ak, cin, H, W, p_in)
+    if cin < 16:        # the network input: NCHW through its strides
+        xa0.mode, xa0.sn, xa0.sc, xa0.sy, xa0.sx = L.ACT_STRIDED, cin * H * W, H * W, W, 1
+    g, _ = layout_acts(gk, cout, H, W, p_out)
+    if gk == "plain" and cout % 4:
+        as_strided_act(g)
+    fa.xa0, fa.xa1 = xa0, (xa1 if xa1 is not None else L.Act())
+    fa.Cin, fa.CinPad, fa.Cout, fa.CoutPad = cin, pad16(cin), cout, pad16(cout)
+    d = fa.d
+    d.a0, d.math, d.Cout, d.CoutPad, d.N, d.H, d.W, d.taps = g, L.MATH_BF16X3, cin, pad16(cin), N, H, W, 9
+    if cin >= 16:
+        d.out, d.wpk = 256, 256
+        d.out_pstride = (split or cin) + OPAD
+        if split:
+            d.out2, d.out_split, d.out2_pstride = 256, split, cin - split + O2PAD
+    fa.slab = 256
+    return fa
 
 
 # ---- canaries around device outputs (tests/test_gpu_optim.py, tests/test_gpu_tokens_edges.py) -----------------------------------------

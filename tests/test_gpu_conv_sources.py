@@ -23,12 +23,9 @@ from tests.helpers import AdHocConv
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 B16 = L.MATH_BF16X3
-NAN = float("nan")
-PADC, COFF = 12, 4          # raw tensors: channel offset COFF inside a buffer of C + PADC floats per pixel
-APAD, AOFF = 20, 8          # the dA tensor of a dz source (aux_pstride differs from pstride)
-TPAD, TOFF = 16, 8          # tables: column offset TOFF (bn_coff) inside rows of C + TPAD
-OPAD, OOFF = 12, 4          # outputs
-O2PAD, O2OFF = 20, 8        # second output (out2)
+NAN = T.NAN
+PADC, COFF, APAD, AOFF, TPAD, TOFF, OPAD, OOFF, O2PAD, O2OFF = T.PADC, T.COFF, T.APAD, T.AOFF, T.TPAD, T.TOFF, T.OPAD, T.OOFF, T.O2PAD, T.O2OFF
+_wide, _interior, _device_source = T.wide, T.interior, T.device_source      # (shared with tests/test_gpu_tile_edges.py)
 WORST = {}                  # group -> [kernel ratio, torch float32 ratio]
 
 
@@ -75,51 +72,6 @@ def _narrow(opt):
         yield
     finally:
         lib.hpfg_set_option(L.OPT_NARROW_DEEP, prev)
-
-
-def _wide(t, pad=PADC, coff=COFF):
-    """CPU tensor [..., C] -> (NaN-filled device buffer [..., C + pad] with t at channel offset coff, address of its first interior element)"""
-    c = t.shape[-1]
-    buf = torch.full(tuple(t.shape[:-1]) + (c + pad,), NAN, device=DEV)
-    buf[..., coff:coff + c] = t.to(DEV)
-    return buf, buf.data_ptr() + 4 * coff
-
-
-def _interior(buf, c, coff):
-    """(interior [..., c], True when every element around it is still NaN)"""
-    mask = torch.ones(buf.shape[-1], dtype=torch.bool, device=buf.device)
-    mask[coff:coff + c] = False
-    return buf[..., coff:coff + c], bool(torch.isnan(buf[..., mask]).all())
-
-
-def _device_source(s, H, W):
-    """conv_source dict -> (a0, a1 or None, tensors to keep alive) on the device, every tensor and table inside a wider NaN-filled one"""
-    kind, C_, keep = s["kind"], s["C"], []
-    a = L.Act()
-    zb, a.z = _wide(s["z"])
-    keep.append(zb)
-    ca = s["z"].shape[-1]
-    a.C, a.Hs, a.Ws, a.pstride = ca, s["z"].shape[1], s["z"].shape[2], ca + PADC
-    if kind == "plain":
-        a.mode = L.ACT_PLAIN
-        return a, None, keep
-    tb = torch.full((L.BN_ROWS, ca + TPAD), NAN, device=DEV)
-    tb[:, TOFF:TOFF + ca] = s["tab"].to(DEV)
-    keep.append(tb)
-    a.bn, a.bn_stride, a.bn_coff = L.ptr(tb), ca + TPAD, TOFF
-    a.drop_p, a.drop_seed = s["p"], s["dseed"]
-    a.mode = {"bnact": L.ACT_BNACT, "pool": L.ACT_BNACT_POOL, "cat": L.ACT_BNACT, "dz": L.ACT_DZ}[kind]
-    a1 = None
-    if kind == "dz":
-        ab, a.aux = _wide(s["dA"], APAD, AOFF)
-        a.aux_pstride = ca + APAD
-        keep.append(ab)
-    if kind == "cat":
-        a1 = L.Act()
-        ub, a1.z = _wide(s["u"])
-        keep.append(ub)
-        a1.mode, a1.C, a1.Hs, a1.Ws, a1.pstride = L.ACT_UP2X, C_ - ca, s["u"].shape[1], s["u"].shape[2], C_ - ca + PADC
-    return a, a1, keep
 
 
 def _inputs_untouched(keep):

@@ -492,20 +492,28 @@ def test_source_restatements_equal_torch_float64_ops():
     assert float((T.nchw(dzv) - zr.grad).abs().max()) <= 1e-12 * float(zr.grad.abs().max()) and float(dzd.min()) >= 0
 
 
-def _conv_case_checks():
-    """(tag, group, float64 reference, bound, emulated result) of every case of tests/test_gpu_conv_sources.py, from its CPU inputs"""
+def _emu(kind, a, w, b=None, g=None):
+    """the split-product emulation (oracle.bf16x3_ref: three kept products, fp32 accumulation) of a conv / dgrad / wgrad on float64-derived
+    NHWC operands"""
     from oracle import bf16x3_ref
     from tests import helpers as T
+    pad = w.shape[-1] // 2
+    with bf16x3_ref.math_mode("bf16x3"):
+        if kind == "conv":
+            return bf16x3_ref.conv2d(T.nchw(a).float(), w, b, padding=pad).permute(0, 2, 3, 1).double()
+        if kind == "dgrad":      # (the input gradient alone: no weight gradient is formed)
+            xr = torch.zeros(g.shape[0], w.shape[1], g.shape[1], g.shape[2], requires_grad=True)
+            bf16x3_ref.conv2d(xr, w, None, padding=pad).backward(T.nchw(g).float())
+            return xr.grad.permute(0, 2, 3, 1).double()
+        wr = w.clone().requires_grad_(True)
+        bf16x3_ref.conv2d(T.nchw(a).float(), wr, None, padding=pad).backward(T.nchw(g).float())
+        return wr.grad.double()
 
-    def emu(kind, a, w, b=None, g=None):
-        pad = w.shape[-1] // 2
-        with bf16x3_ref.math_mode("bf16x3"):
-            if kind == "conv":
-                return bf16x3_ref.conv2d(T.nchw(a).float(), w, b, padding=pad).permute(0, 2, 3, 1).double()
-            xr = (T.nchw(a).float() if a is not None else torch.zeros(g.shape[0], w.shape[1], g.shape[1], g.shape[2])).requires_grad_(True)
-            wr = w.clone().requires_grad_(True)
-            bf16x3_ref.conv2d(xr, wr, None, padding=pad).backward(T.nchw(g).float())
-            return xr.grad.permute(0, 2, 3, 1).double() if kind == "dgrad" else wr.grad.double()
+
+def _conv_case_checks():
+    """(tag, group, float64 reference, bound, emulated result) of every case of tests/test_gpu_conv_sources.py, from its CPU inputs"""
+    from tests import helpers as T
+    emu = _emu
 
     for c in T.FWD3_CASES + [T.FWD3_PERSISTENT] + [k + (None,) for k in T.FWD1_CASES]:
         kind, p, N, H, W, cin, cout = c[:7]
@@ -559,3 +567,146 @@ def test_split_product_emulation_stays_within_the_bound_on_every_case():
         assert r <= 1.0, f"{tag}: the emulation is {r:.3g} x the bound off the float64 result"
     for group in sorted(worst):
         print(f"[conv_sources] {group} (CPU emulation): largest error / bound = {worst[group]:.3g}")
+
+
+# ---- the cases of tests/test_gpu_tile_edges.py (whole-tile kernels) ------------------------------------------------------------------------
+def test_tile_edge_cases_reach_the_kernels_and_the_walk_cases_walk():
+    """The launch geometry the GPU tests rely on, from the library's host side: every thin case goes to conv_thin_kernel (a multiple of 8
+    rows, not the chunked kernel's count), every fused case has an instantiation, the tile-count edges are what their names say, and in the
+    walk cases every workgroup's tile loop runs twice (three times with one workgroup per CU) on an uneven, non-square grid of tiles."""
+    import ctypes as C
+    from hpfg_amd import _lib as L
+    from tests import helpers as T
+    lib = L.load()
+    seen = set()
+    for case in T.THIN_CASES:
+        kind, _, N, H, W, _, _, edge = case
+        rows = lib.hpfg_conv_stat_rows(C.byref(T.thin_args(case)))
+        assert rows > 0 and rows % 8 == 0 and rows != lib.hpfg_conv_stat_rows(C.byref(T.thin_args(case, L.MATH_BF16X3 | T.OLD_KERNEL))), case
+        nwork = N * (H // 16) * (W // 16)
+        if edge == "walk":
+            assert T.walk_conditions(nwork, rows, W // 16, H // 16, T.THIN_INST[kind][2]), (case, rows)
+        elif edge:
+            assert nwork < rows and (edge == "one") == (nwork == 1), (case, rows)
+        seen.add((kind, edge))
+    assert seen >= {(k, e) for k in T.THIN_INST for e in ("one", "few", "walk")}
+    seen = set()
+    for case in T.FUSED_CASES:
+        ak, _, gk, _, N, H, W, cin, _, _, edge = case
+        grid = lib.hpfg_fused_bwd_grid(C.byref(T.fused_args(case)))
+        assert grid > 0, (case, lib.hpfg_last_error())
+        inst = [v for v in T.FUSED_INST.values() if v[:3] == (ak, gk, cin)]
+        assert len(inst) == 1, case
+        nwork = N * (H // 16) * (W // 16)
+        if edge == "walk":
+            assert T.walk_conditions(nwork, grid, W // 16, H // 16, inst[0][4]), (case, grid)
+        elif edge:
+            assert nwork < grid and (edge == "one") == (nwork == 1), (case, grid)
+        seen.add((ak, gk, cin, edge))
+    assert seen >= {v[:3] + (e,) for v in T.FUSED_INST.values() for e in ("one", "few", "walk")}
+    assert set(T.QUAD_FUSED) <= set(T.FUSED_CASES)
+    for N, H, W, cin, _, _, _ in T.FIRST_CASES:
+        assert H % 16 == 0 and W % 16 == 0 and 64 <= W <= 512 and cin in (1, 3)
+    assert any(N * H > 768 for N, H, *_ in T.FIRST_CASES) and {c[2] for c in T.FIRST_CASES} >= {64, 80, 272, 512}
+
+
+def _ratio(got, ref, bound):
+    return float(((got - ref).abs() / bound).max())
+
+
+def test_tile_edge_cases_emulation_stays_within_the_bound():
+    """The condition on the inputs of tests/test_gpu_tile_edges.py, as for the chunked kernels above: every source passes its LeakyReLU guard
+    (conv_source asserts it), the bounds are positive, and the split-product emulation -- torch float32 for the streaming first-layer kernel,
+    which multiplies in fp32 -- stays inside the bound of every case, so the float64 reference alone passes."""
+    from tests import helpers as T
+    worst = {}
+
+    def within(group, tag, got, ref, bound):
+        assert bool(torch.isfinite(ref).all()) and float(bound.min()) > 0, tag
+        r = _ratio(got, ref, bound)
+        worst[group] = max(worst.get(group, 0.0), r)
+        assert r <= 1.0, f"{tag}: the emulation is {r:.3g} x the bound off the float64 result"
+
+    for case in T.THIN_CASES:
+        d = T.thin_case(case)
+        got = _emu("dgrad", None, d["w"], g=d["s"]["v"]) if case[0] == "dz" else _emu("conv", d["s"]["v"], d["w"], d["b"])
+        within("A", f"thin {case}", got, d["ref"], d["bound"])
+        assert d["f32"] <= 1.0, case
+    for case in T.FUSED_CASES:
+        d = T.fused_case(case)
+        if d["dx"] is not None:
+            within("B", f"fused dX {case}", _emu("dgrad", None, d["w"], g=d["sg"]["v"]), *d["dx"][:2])
+        within("B", f"fused dW {case}", _emu("wgrad", d["sa"]["v"], d["w"], g=d["sg"]["v"]), *d["dw"][:2])
+    for N, H, W, cin, p in sorted({c[:5] for c in T.FIRST_CASES}):
+        d = T.first_case(N, H, W, cin, p)
+        assert d["f32"] <= 1.0 and float(d["b_stream"].min()) > 0 and bool((d["b_stream"] < d["b_tile"]).all()), (N, H, W, cin, p)
+        w0 = torch.zeros(16, cin, 3, 3)
+        within("C", f"first layer {(N, H, W, cin, p)}", _emu("wgrad", d["sx"]["v"], w0, g=d["sg"]["v"]), d["ref"], d["b_tile"])
+    for case in T.QUAD_DGRAD:
+        kind, p, N, H, W, cin, cout = case[:7]
+        s = T.conv_source(kind, T.case_seed(*case), N, H, W, cout, p)
+        w, _ = T.adhoc_weights(cin, cout, 9, T.case_seed(*case))
+        within("D", f"dgrad {case}", _emu("dgrad", None, w, g=s["v"]), *T.dgrad_ref_bound(s["v"], s["d"], w))
+    for case in T.QUAD_WGRAD:
+        ak, pa, gk, pg, N, H, W, cin, cout, taps = case
+        sa, sg = T.conv_source(ak, T.case_seed(*case), N, H, W, cin, pa), T.conv_source(gk, T.case_seed(*case) + 1, N, H, W, cout, pg)
+        w, _ = T.adhoc_weights(cin, cout, taps, T.case_seed(*case))
+        within("D", f"wgrad {case}", _emu("wgrad", sa["v"], w, g=sg["v"]), *T.wgrad_ref_bound(sa["v"], sa["d"], sg["v"], sg["d"], w.shape))
+    for group in sorted(worst):
+        print(f"[tile_edges] {group} (CPU emulation): largest error / bound = {worst[group]:.3g}")
+
+
+def test_tile_edge_bounds_tell_three_wrong_kernels_apart_on_the_walk_cases():
+    """The bounds are tight enough to matter.  Three wrong kernels restated in float64 on the walk cases, each of which must leave the bound:
+      halo   the left halo column of one interior tile read as zero -- forward conv and dgrad;
+      tile   the pixels of one tile missing from the weight gradient.  The bound grows with (N H W + 2) 2^-24 sum|a||g|, which at the 140 to
+             200 thousand pixels of a walk is far more than a unit-scale tile contributes; the walk cases carry one tile of 8 x the amplitude
+             (helpers.walk_hot) and it is that tile whose absence must show;
+      hi     the hi * lo + lo * hi products dropped (bf16 operands) -- forward conv and dgrad, whose bound is dominated by the split term.  On
+             the weight gradient of a walk case the summation term dominates instead and this mutant stays inside: printed, not required."""
+    import torch.nn.functional as F
+    from torch.nn import grad as G
+    from oracle import bf16x3_ref
+    from tests import helpers as T
+    hi = lambda t: bf16x3_ref.split(t.float())[0].double()
+    y0, x0, _ = T.HOT
+
+    def conv(a, w, b):
+        return F.conv2d(T.nchw(a), w.double(), None if b is None else b.double(), padding=1).permute(0, 2, 3, 1)
+
+    def dgrad(g, w):
+        return F.conv_transpose2d(T.nchw(g), w.double(), padding=1).permute(0, 2, 3, 1)
+
+    def halo_mutant(op, src, n, ref):
+        cut = src[n:n + 1].clone()
+        cut[0, y0 - 1:y0 + 17, x0 - 1] = 0.0
+        mut = ref.clone()
+        mut[n, y0:y0 + 16, x0:x0 + 16] = op(cut)[0, y0:y0 + 16, x0:x0 + 16]
+        return mut
+
+    for case in [c for c in T.THIN_CASES if c[-1] == "walk"]:
+        d, n = T.thin_case(case), case[2] // 2
+        v, w = d["s"]["v"], d["w"]
+        if case[0] == "dz":
+            op, low = (lambda t: dgrad(t, w)), dgrad(hi(v), hi(w))
+        else:
+            op, low = (lambda t: conv(t, w, d["b"])), conv(hi(v), hi(w), d["b"])
+        assert float((op(v[n:n + 1])[0] - d["ref"][n]).abs().max()) <= 1e-9 * float(d["ref"].abs().max())      # (the restatement is the reference's op)
+        r_halo, r_hi = _ratio(halo_mutant(op, v, n, d["ref"]), d["ref"], d["bound"]), _ratio(low, d["ref"], d["bound"])
+        print(f"[tile_edges] mutants thin {case}: halo {r_halo:.3g}, hi-only {r_hi:.3g} x the bound")
+        assert r_halo > 1.0 and r_hi > 1.0, (case, r_halo, r_hi)
+    for case in [c for c in T.FUSED_CASES if c[-1] == "walk"]:
+        d, n = T.fused_case(case), case[4] // 2
+        a, g, w = d["sa"]["v"], d["sg"]["v"], d["w"]
+        r_halo = r_hi = float("nan")      # (the first layer has no dX)
+        if d["dx"] is not None:
+            ref, bound, _ = d["dx"]
+            r_halo, r_hi = _ratio(halo_mutant(lambda t: dgrad(t, w), g, n, ref), ref, bound), _ratio(dgrad(hi(g), hi(w)), ref, bound)
+            assert r_halo > 1.0 and r_hi > 1.0, (case, r_halo, r_hi)
+        ref, bound, _ = d["dw"]
+        only = torch.zeros_like(a[n:n + 1])
+        only[0, y0:y0 + 16, x0:x0 + 16] = a[n, y0:y0 + 16, x0:x0 + 16]
+        r_tile = _ratio(ref - G.conv2d_weight(T.nchw(only), tuple(w.shape), T.nchw(g[n:n + 1]), padding=1), ref, bound)
+        r_hi_dw = _ratio(G.conv2d_weight(T.nchw(hi(a)), tuple(w.shape), T.nchw(hi(g)), padding=1), ref, bound)
+        print(f"[tile_edges] mutants fused {case}: halo {r_halo:.3g}, hi-only {r_hi:.3g} (dX); missing tile {r_tile:.3g}, hi-only {r_hi_dw:.3g} (dW) x the bound")
+        assert r_tile > 1.0, (case, r_tile)
