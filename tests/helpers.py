@@ -561,15 +561,16 @@ def _split_bound(S, T, chain, split=True):
     return (3.0 * 2.0 ** -16 * S if split else 0.0) + (T + 2) * U24 * S + chain
 
 
-def conv_ref_bound(a, da, w, b):
-    """a, da [N,H,W,Cin] float64 (value, delta), w [Cout,Cin,k,k], b [Cout] or None -> (F.conv2d in float64, bound), both [N,H,W,Cout]"""
+def conv_ref_bound(a, da, w, b, split=True):
+    """a, da [N,H,W,Cin] float64 (value, delta), w [Cout,Cin,k,k], b [Cout] or None -> (F.conv2d in float64, bound), both [N,H,W,Cout].
+    split=False: without the 3 * 2^-16 * S term of the split products (the first layer's kernels: fmaf chains in exact fp32)"""
     pad = w.shape[-1] // 2
     w64, x = w.double(), nchw(a)
     ref = F.conv2d(x, w64, None if b is None else b.double(), padding=pad)
     S = F.conv2d(x.abs(), w64.abs(), None if b is None else b.double().abs(), padding=pad)
     chain = F.conv2d(nchw(da), w64.abs(), None, padding=pad)
     T = w[0].numel() + (0 if b is None else 1)
-    return ref.permute(0, 2, 3, 1).contiguous(), _split_bound(S, T, chain).permute(0, 2, 3, 1).contiguous()
+    return ref.permute(0, 2, 3, 1).contiguous(), _split_bound(S, T, chain, split).permute(0, 2, 3, 1).contiguous()
 
 
 def dgrad_ref_bound(g, dg, w):
@@ -2094,3 +2095,402 @@ def dense_case(n, T=0.7):
         U = torch.cat([l2norm_f64(s)[0].flatten(1), l2norm_f64(t)[0].flatten(1)])
         top = max(top, ntxent_f64((U @ U.t()), n, T)[2])
     return dict(sg=sg, sd=sd_, tg=tg, td=td, ref=out[torch.float64], yard=out[torch.float32], top=top)
+
+
+# ---- the first conv and the stand-alone backward kernels (tests/test_gpu_standalone_edges.py, tests/test_standalone_laws_host.py) --------
+# conv_first_kernel / conv_first_mfma_kernel (csrc/conv.hip), upsample_bwd_kernel, pool_scatter_kernel, dropout_mask_kernel (csrc/misc.hip),
+# channel_sum_stage1 / 2, slab_reduce_multi_kernel (csrc/wgrad.hip), bn_bwd_reduce_kernel, bn_bwd_reduce_pool_kernel (csrc/bn.hip).
+# One rule: max |got - ref| / bound <= 1 against a float64 restatement, the bound (n + 2) * 2^-24 * sum|term| of a sum of n fp32 terms formed
+# in exact fp32 (one more rounding where the result is rounded once more to float).  Every law takes `mutation`: a named wrong variant that
+# tests/test_standalone_laws_host.py shows to lie at least 4 bounds off on some case below.
+STANDALONE_MUTATIONS = {
+    "first": ("halo_not_zero", "second_tile_skipped", "stats_over_partial_tiles", "taps_transposed"),
+    "upbwd": ("window_one_short", "last_xcd_span_dropped", "sums_of_first_trip_only"),
+    "chansum": ("idle_rows_not_zero", "last_trip_dropped"),
+    "slab": ("slab_lane_16_dropped", "pad_rows_included", "scalar_path_quad_tail_dropped"),
+    "poolbwd": ("last_max_wins", "slope_from_dA_sign"),
+}
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def mutation_ratio(got, ref, bound):
+    """largest |got - ref| / bound; an element that is not finite, or that differs where the bound is 0 (a bit-for-bit output), counts as inf"""
+    d = (got.double() - ref.double()).abs()
+    b = bound if torch.is_tensor(bound) else torch.full_like(d, float(bound))
+    r = torch.where(d > 0, d / b, torch.zeros_like(d))
+    r = torch.where(torch.isfinite(got.double()), r, torch.full_like(r, float("inf")))
+    return float(r.max())
+
+
+# -- 1. first conv forward.  (N, H, W, cin); statistics are requested wherever the launcher admits them (whole 16 x 16 tiles)
+FIRST_FWD_SHAPES = ((2, 16, 16), (1, 32, 48), (1, 1, 1), (1, 5, 40), (2, 17, 31))      # one tile an image | 6 tiles | partial tiles, H below the tile
+FIRST_FWD_WALK = ((33, 32, 256, (1, 3)), (23, 40, 250, (1, 2)))                        # 1056 whole / 1104 partial tiles on 1024 workgroups
+FIRST_FWD_CASES = ([(n, h, w, c) for n, h, w in FIRST_FWD_SHAPES for c in (1, 2, 3, 4)] +
+                   [(n, h, w, c) for n, h, w, cs in FIRST_FWD_WALK for c in cs])
+FIRST_FWD_LAYOUT_SHAPES = ((2, 17, 31), (2, 16, 16))
+FIRST_FWD_INF = (1, 32, 48)
+FIRST_FWD_INF_AT = ((5, 16), (20, 15), (0, 0))      # column 0 of the tile at x0 = 16 | the halo column of that tile (LDS offset 0 of its rows, which the
+#                                                     padding k-steps of the matrix-core form address) | the image's first pixel
+FIRST_FWD_REFUSED_STATS = (2, 24, 32)               # statistics over partial tiles: refused by the launcher (stats_over_partial_tiles)
+FIRST_GRID_CAP = 1024
+
+
+def first_fwd_geometry(N, H, W):
+    """conv_first_grid (csrc/conv.hip): (workgroups = rows of partial sums, tiles)"""
+    nwork = N * _cdiv(H, 16) * _cdiv(W, 16)
+    return min(nwork, FIRST_GRID_CAP), nwork
+
+
+def first_fwd_stats(H, W):
+    return H % 16 == 0 and W % 16 == 0
+
+
+def first_fwd_f64(x, w, b, mutation=None):
+    """x [N,H,W,cin] float64, w [16,cin,3,3], b [16] -> the float64 convolution [N,H,W,16] (conv_ref_bound's reference), or a wrong variant"""
+    w64, xn = w.double(), nchw(x)
+    if mutation == "taps_transposed":
+        w64 = w64.transpose(-1, -2)
+    if mutation == "halo_not_zero":
+        out = F.conv2d(F.pad(xn, (1, 1, 1, 1), mode="replicate"), w64, b.double())
+    else:
+        out = F.conv2d(xn, w64, b.double(), padding=1)
+    out = out.permute(0, 2, 3, 1).contiguous()
+    if mutation == "second_tile_skipped":
+        N, H, W, C_ = out.shape
+        assert first_fwd_stats(H, W)
+        grid, nwork = first_fwd_geometry(N, H, W)
+        t = out.reshape(N, H // 16, 16, W // 16, 16, C_).permute(0, 1, 3, 2, 4, 5).reshape(nwork, 16, 16, C_).clone()
+        t[grid:] = t[:nwork - grid]          # tile wk >= grid keeps what its workgroup computed for tile wk - grid
+        out = t.reshape(N, H // 16, W // 16, 16, 16, C_).permute(0, 1, 3, 2, 4, 5).reshape(N, H, W, C_).contiguous()
+    return out
+
+
+def first_sums_f64(x, w, b, mutation=None):
+    """(sum z, sum z^2) [2][16] in float64 and their bound (n + 2) * 2^-24 * sum|term| (fwd_sums_ratio's); stats_over_partial_tiles: summed over
+    the whole 16 x 16 tiles of the zero-padded image, the pixels outside the image included"""
+    N, H, W, _ = x.shape
+    z = first_fwd_f64(x, w, b).reshape(-1, 16)
+    n = z.shape[0]
+    bound = torch.stack([(n + 2) * U24 * t.abs().sum(0) for t in (z, z * z)])
+    if mutation == "stats_over_partial_tiles":
+        xp = F.pad(x, (0, 0, 0, _cdiv(W, 16) * 16 - W, 0, _cdiv(H, 16) * 16 - H))
+        z = first_fwd_f64(xp, w, b).reshape(-1, 16)
+    return torch.stack([z.sum(0), (z * z).sum(0)]), bound
+
+
+@functools.lru_cache(maxsize=None)
+def first_fwd_case(N, H, W, cin):
+    """CPU data of a FIRST_FWD_CASES entry: input x [N,H,W,cin] (float32), weights, float64 reference and bound (no split term), the ratio
+    torch float32 reaches.  Read-only."""
+    seed = case_seed("firstfwd", N, H, W, cin)
+    x = conv_source("plain", seed, N, H, W, cin)["z"]
+    w, b = adhoc_weights(cin, 16, 9, seed)
+    ref, bound = conv_ref_bound(x.double(), torch.zeros(N, H, W, cin, dtype=torch.float64), w, b, split=False)
+    return dict(x=x, w=w, b=b, ref=ref, bound=bound, f32=f32_conv_ratio("conv", ref, bound, x.double(), w, b), seed=seed)
+
+
+# -- 2. hpfg_upsample2x_bwd(_sums).  (N, Hl, Wl, C)
+UPB_MAXDIM = 512
+UPBWD_SA_CASES = ((1, 1, 1, 4), (2, 1, 7, 8), (2, 7, 1, 8), (2, 2, 2, 4),
+                  (1, 5, 6, 12), (1, 3, 3, 260),            # C/4 does not divide 256: the plain entry works, _sums refuses
+                  (1, 9, 7, 256),
+                  (1, 1, 511, 4), (1, 511, 1, 4),           # Hl + Wl == 512: the last admitted tap table
+                  (1, 16, 30, 16),                          # 1920 quads, 8 workgroups: one per XCD, the last span short
+                  (1, 13, 25, 48),                          # 3900 quads, 16 workgroups: two per XCD span (C/4 = 12: no sums)
+                  (1, 20, 23, 20),                          # 2300 quads, 9 workgroups: not a multiple of 8, the linear path (C/4 = 5: no sums)
+                  (3, 64, 64, 128))                         # 393 216 quads on the capped grid of 1024: one and a half trips per workgroup
+UPBWD_REFUSED = (1, 2, 511, 4)                              # Hl + Wl == 513
+UPBWD_SUMS_C = (4, 8, 16, 48, 64, 128, 256)                 # 48: 256 % 12 != 0, refused
+UPBWD_SUMS_CASES = tuple((2, 6, 5, c) for c in UPBWD_SUMS_C) + UPBWD_SA_CASES      # every case goes through both entries
+
+
+def upbwd_sums_admitted(C_):
+    """the launcher's rule for channel sums (hpfg_upsample2x_bwd_sums)"""
+    return C_ % 4 == 0 and 4 <= C_ <= 256 and 256 % (C_ // 4) == 0
+
+
+def upbwd_geometry(N, Hl, Wl, C_):
+    """hpfg_upsample2x_bwd_blocks and the XCD split of upsample_bwd_kernel: dict(total quads, blocks, nxcd, gx = workgroups per XCD span,
+    span = quads per XCD in whole 256-thread rows, trips = the most trips a workgroup's loop takes)"""
+    total = N * Hl * Wl * (C_ // 4)
+    blocks = min(max(_cdiv(total, 256), 1), 1024)
+    nxcd = 8 if blocks % 8 == 0 else 1
+    span = _cdiv(_cdiv(total, nxcd), 256) * 256
+    gx = blocks // nxcd
+    return dict(total=total, blocks=blocks, nxcd=nxcd, gx=gx, span=span, trips=_cdiv(_cdiv(min(span, total), 256), gx))
+
+
+def upbwd_trip_of(geo):
+    """trip index (0, 1, ..) of the workgroup loop in which every flat output quad i = pixel * C/4 + quad is produced, and its XCD"""
+    i = torch.arange(geo["total"])
+    xcd = i // geo["span"]
+    return ((i - xcd * geo["span"]) // 256) // geo["gx"], xcd
+
+
+def upbwd_mutant(g, mutation, geo):
+    """upbwd_f64's value with one thing wrong.  window_one_short: the gather window of hpfg_up_taps runs over outputs 2 lo - 2 .. 2 lo + 4, of
+    which 2 lo + 2 is the last that ever carries weight (up2x_window_reach) -- the variant loses that one.  last_xcd_span_dropped: the quads
+    of the eighth XCD span are never written (0)."""
+    (my, _), (mx, _) = up2x_matrix(g.shape[1] // 2), up2x_matrix(g.shape[2] // 2)
+    if mutation == "window_one_short":
+        for m in (my, mx):
+            for lo in range(m.shape[1]):
+                if 2 * lo + 2 < m.shape[0]:
+                    m[2 * lo + 2, lo] = 0.0
+    d = torch.einsum("yi,nyxc,xj->nijc", my, g.double(), mx)
+    if mutation == "last_xcd_span_dropped" and geo["nxcd"] == 8:
+        _, xcd = upbwd_trip_of(geo)
+        q = d.reshape(-1, 4).clone()
+        q[xcd == 7] = 0.0
+        d = q.reshape(d.shape)
+    return d
+
+
+def up2x_window_reach(Lo):
+    """largest o - 2 lo over the outputs o that read source index lo with the law's fp32 weights (up2x_matrix)"""
+    m, _ = up2x_matrix(Lo)
+    o, lo = torch.nonzero(m, as_tuple=True)
+    return int((o - 2 * lo).max()), int((o - 2 * lo).min())
+
+
+def upbwd_sums_f64(dU, geo, mutation=None):
+    """channel sums [C] of dU [N,Hl,Wl,C] in float64 and the bound (n + 2) * 2^-24 * sum|dU|, n = N Hl Wl.  sums_of_first_trip_only: a
+    workgroup's sums forget every trip of its loop but the first"""
+    dU = dU.double()
+    C_ = dU.shape[-1]
+    n = dU.numel() // C_
+    bound = (n + 2) * U24 * dU.abs().reshape(-1, C_).sum(0)
+    if mutation == "sums_of_first_trip_only":
+        trip, _ = upbwd_trip_of(geo)
+        dU = torch.where((trip == 0).reshape(-1, C_ // 4, 1), dU.reshape(-1, C_ // 4, 4), torch.zeros((), dtype=torch.float64))
+    return dU.reshape(-1, C_).sum(0), bound
+
+
+@functools.lru_cache(maxsize=None)
+def upbwd_case(N, Hl, Wl, C_):
+    """gradient g [N,2Hl,2Wl,C] (float32), float64 law and bound of upbwd_f64, the ratio of the same law in float32.  Read-only."""
+    gen = torch.Generator().manual_seed(case_seed("upbwd", N, Hl, Wl, C_))
+    g = torch.randn(N, 2 * Hl, 2 * Wl, C_, generator=gen)
+    ref, bound = upbwd_f64(g)
+    (my, _), (mx, _) = up2x_matrix(Hl), up2x_matrix(Wl)
+    f32 = torch.einsum("yi,nyxc,xj->nijc", my.float(), g, mx.float())
+    bound = torch.clamp(bound, min=1e-300)
+    return dict(g=g, ref=ref, bound=bound, f32=float(((f32.double() - ref).abs() / bound).max()))
+
+
+# -- 3. hpfg_channel_sum_partials / hpfg_channel_sum.  (npix, C, pstride)
+CHANSUM_CASES = ((1, 4, 4), (7, 16, 16),                    # smallest vector cases
+                 (1000, 12, 12),                            # 3 quads, 85 pixel lanes, one thread idle
+                 (300, 256, 256),                           # 4 pixel lanes
+                 (5000, 16, 24),                            # a slice of a wider buffer, vector path
+                 (5000, 16, 18),                            # stride not a multiple of 4: the scalar path with C % 4 == 0
+                 (5000, 1, 1), (5000, 2, 2), (5000, 3, 3), (5000, 5, 5), (5000, 9, 9), (5000, 255, 255),      # scalar path: the engine's class counts
+                 (8197, 256, 256),                          # second trip of the 4x-unrolled vector loop on the capped grid of 512
+                 (65539, 2, 2),                             # second trip of the scalar loop
+                 (100, 64, 64))                             # 25 workgroups, 7 with pixels: 18 rows of zeros
+CHANSUM_OFFSET = (999, 16, 20, 2)                           # npix, C, pstride, base offset in floats: the vector path at a 4-byte-aligned address
+CHANSUM_IDLE = (100, 64, 64)
+
+
+def chansum_geometry(npix, C_, pstride):
+    """hpfg_channel_sum_blocks (sized by 256 / C pixel lanes) and what channel_sum_stage1 does with it: dict(blocks, vec, lanes = pixels per
+    workgroup and sweep of the path taken, busy = workgroups that own a pixel, trips of the loop, sweep = pixels per trip of the launch)"""
+    if C_ < 1 or C_ > 256 or npix < 1:
+        return dict(blocks=0)
+    blocks = min(_cdiv(npix, 256 // C_), 512)
+    vec = C_ % 4 == 0 and pstride % 4 == 0
+    lanes = 256 // (C_ // 4) if vec else 256 // C_
+    sweep = blocks * lanes * (4 if vec else 1)
+    return dict(blocks=blocks, vec=vec, lanes=lanes, busy=min(blocks, _cdiv(npix, lanes)), trips=_cdiv(npix, sweep), sweep=sweep)
+
+
+def chansum_f64(g, geo, mutation=None):
+    """g [npix, C] -> (float64 channel sums [C], bound (npix + 2) * 2^-24 * sum|g|).  idle_rows_not_zero: every workgroup without a pixel leaves
+    a stale 1.0 per channel; last_trip_dropped: the pixels of the last trip of a loop that runs more than once are lost"""
+    g = g.double()
+    bound = (g.shape[0] + 2) * U24 * g.abs().sum(0)
+    s = g.sum(0)
+    if mutation == "idle_rows_not_zero":
+        s = s + float(geo["blocks"] - geo["busy"])
+    if mutation == "last_trip_dropped" and geo["trips"] > 1:
+        s = g[:(geo["trips"] - 1) * geo["sweep"]].sum(0)
+    return s, bound
+
+
+@functools.lru_cache(maxsize=None)
+def chansum_case(npix, C_, pstride, off=0):
+    """buffer [off + npix * pstride] (float32; NaN pattern outside the C channels of every pixel is the caller's business: here the other
+    floats are random), the interior g [npix, C], float64 sums, bound, float32 ratio.  Read-only."""
+    gen = torch.Generator().manual_seed(case_seed("chansum", npix, C_, pstride, off))
+    buf = torch.randn(off + npix * pstride, generator=gen)
+    geo = chansum_geometry(npix, C_, pstride)
+    if geo["trips"] > 1:          # the few pixels of the last trip would vanish in the summation bound of 10^4 .. 10^5 unit terms: they carry 2^12 x
+        buf[off:].reshape(npix, pstride)[(geo["trips"] - 1) * geo["sweep"]:] *= 4096.0          # the amplitude (the walk_hot device)
+    g = buf[off:].reshape(npix, pstride)[:, :C_]
+    ref, bound = chansum_f64(g, geo)
+    return dict(buf=buf, g=g, ref=ref, bound=bound, f32=float(((g.sum(0).double() - ref).abs() / bound).max()))
+
+
+# -- 4. hpfg_slab_reduce_multi on synthetic slabs.  layer = (taps, Cin, CinPad, Cout, CoutPad)
+SLAB_LAYERS = ((9, 3, 16, 16, 16), (1, 40, 48, 8, 16), (9, 16, 16, 5, 16)) + tuple((1, 1, 1, c, c) for c in (2, 4, 9, 16))
+SLAB_S = (1, 15, 16, 17, 48, 49, 64, 65, 113)               # the edges of the `s + 48 < S` loop and of its 16-strided tail
+SLAB_MIXED_S = (1, 17, 113, 113, 17, 1, 17)                 # one launch, another S per layer
+SLAB_CAP_LAYERS = ((9, 128, 128, 128, 128), (1, 1, 1, 2, 2))      # per = 147 456 > 2048 * 64: the capped grid strides twice
+SLAB_CAP_S = 2
+SLAB_GRID_CAP = 2048
+
+
+def slab_grid(layers):
+    """grid x of hpfg_slab_reduce_multi and the trips its widest layer takes"""
+    mx = max(t * cip * cop for t, _, cip, _, cop in layers)
+    gx = min(_cdiv(mx, 64), SLAB_GRID_CAP)
+    return gx, _cdiv(_cdiv(mx, 64), gx)
+
+
+def slab_reduce_f64(slab, layer, mutation=None):
+    """slab [S][taps][CinPad][CoutPad] -> (dw [Cout][Cin][taps] = sum_s slab[s][tap][ci][co] in float64, bound (S + 2) * 2^-24 * sum|.|).
+    slab_lane_16_dropped: the last slab of each of the 16 interleaved lanes (s >= 16 * ((S - 1) // 16), S > 16) is left out; pad_rows_included:
+    the entries ci >= Cin / co >= Cout are folded onto the last valid row / column; scalar_path_quad_tail_dropped: on the scalar path
+    (taps * CinPad * CoutPad % 4 != 0) the elements behind the last whole quad are lost"""
+    taps, cin, cip, cout, cop = layer
+    s = slab.double()
+    S = s.shape[0]
+    bound = (S + 2) * U24 * s[:, :, :cin, :cout].abs().sum(0).permute(2, 1, 0)
+    if mutation == "slab_lane_16_dropped" and S > 16:
+        s = s[:16 * ((S - 1) // 16)]
+    t = s.sum(0)
+    per = taps * cip * cop
+    if mutation == "scalar_path_quad_tail_dropped" and per % 4:
+        t = t.reshape(-1).clone()
+        t[per - per % 4:] = 0.0
+        t = t.reshape(taps, cip, cop)
+    if mutation == "pad_rows_included" and (cip > cin or cop > cout):
+        t = t.clone()
+        t[:, cin - 1] += t[:, cin:].sum(1)
+        t[:, :, cout - 1] += t[:, :, cout:].sum(2)
+    return t[:, :cin, :cout].permute(2, 1, 0).contiguous(), bound
+
+
+@functools.lru_cache(maxsize=None)
+def slab_case(layer, S):
+    """slab [S][taps][CinPad][CoutPad] float32 with NaN in every padded entry ("nobody's result"), float64 law, bound, float32 ratio"""
+    taps, cin, cip, cout, cop = layer
+    gen = torch.Generator().manual_seed(case_seed("slab", *layer, S))
+    slab = torch.randn(S, taps, cip, cop, generator=gen)
+    slab[:, :, cin:] = NAN
+    slab[:, :, :, cout:] = NAN
+    ref, bound = slab_reduce_f64(slab, layer)
+    f32 = slab[:, :, :cin, :cout].sum(0).permute(2, 1, 0)
+    return dict(slab=slab, ref=ref, bound=bound, f32=float(((f32.double() - ref).abs() / bound).max()))
+
+
+# -- 5. hpfg_bn_bwd_reduce, hpfg_bn_bwd_reduce_pool, hpfg_pool_scatter_add
+BNBWD_C = (4, 8, 64, 256, 512, 1024)
+BNBWD_CASES = ((1, 2, 2, 4, 0.0),                           # 4 pixels on 256 pixel lanes
+               (2, 5, 7, 8, 0.3), (3, 12, 16, 64, 0.3), (2, 6, 10, 256, 0.0), (2, 3, 5, 512, 0.0),
+               (2, 3, 5, 1024, 0.3))                        # one pixel lane, eight epilogue passes
+POOLBWD_SHAPES = ((1, 2, 2), (2, 6, 10), (3, 12, 16))       # (N, 2 Hp, 2 Wp)
+POOLBWD_CASES = tuple((n, h, w, c, False) for n, h, w in POOLBWD_SHAPES for c in BNBWD_C) + ((2, 6, 10, 8, True),)      # (.., ties on purpose)
+BNBWD_REFUSED_C = (6, 12, 2048)
+
+
+def bn_bwd_blocks(N, H, W, C_):
+    """hpfg_bn_bwd_blocks"""
+    return min(max(_cdiv(N * H * W, 256 // (C_ // 4) * 16), 1), 1024)
+
+
+def bn_bwd_pool_blocks(N, Hp, Wp, C_):
+    """hpfg_bn_bwd_pool_blocks"""
+    return min(max(_cdiv(N * Hp * Wp, 256 // (C_ // 4) * 2), 1), 2048)
+
+
+def bwd_g_f64(z, dA, tab, p=0.0, seed=0, mutation=None):
+    """g = dA * keep / (1 - p) * slope(z * scale + shift): the gradient in front of the BatchNorm that the backward reductions sum (the g of
+    dz_f64).  slope_from_dA_sign: the LeakyReLU slope decided by the sign of dA"""
+    t, z = tab.double(), z.double()
+    y = lrelu_slope(z, t[L.BN_SCALE], t[L.BN_SHIFT])
+    if mutation == "slope_from_dA_sign":
+        y = torch.where(dA.double() > 0, torch.ones_like(y), torch.full_like(y, 0.01))
+    slope = torch.where(y == 1.0, 1.0, LEAKY32)
+    return dA.double() * keep_f64(z.shape, p, seed) * slope
+
+
+def bwd_sums_f64(g64, z64, tab):
+    """(sum g, sum g xhat) [2][C] in float64 and the bounds of bwd_sums_ratio"""
+    C_ = g64.shape[-1]
+    g, z = g64.reshape(-1, C_), z64.double().reshape(-1, C_)
+    n = g.shape[0]
+    mean, rstd = tab[L.BN_MEAN].double(), tab[L.BN_RSTD].double()
+    val = torch.stack([g.sum(0), (g * ((z - mean) * rstd)).sum(0)])
+    bound = torch.stack([(n + 2) * U24 * g.abs().sum(0), (n + 4) * U24 * rstd * ((g * z).abs().sum(0) + mean.abs() * g.abs().sum(0))])
+    return val, bound
+
+
+@functools.lru_cache(maxsize=None)
+def bnbwd_case(N, H, W, C_, p):
+    """a dz source (conv_source) with its g, the sums and the ratio plain float32 sums reach.  Read-only."""
+    s = conv_source("dz", case_seed("bnbwd", N, H, W, C_, p), N, H, W, C_, p)
+    g64 = bwd_g_f64(s["z"], s["dA"], s["tab"], p, s["dseed"])
+    val, bound = bwd_sums_f64(g64, s["z"], s["tab"])
+    xh = (s["z"] - s["tab"][L.BN_MEAN]) * s["tab"][L.BN_RSTD]
+    g32 = g64.float()
+    f32 = torch.stack([g32.reshape(-1, C_).sum(0), (g32 * xh).reshape(-1, C_).sum(0)])
+    return dict(s=s, g64=g64, val=val, bound=bound, f32=float(((f32.double() - val).abs() / bound).max()))
+
+
+@functools.lru_cache(maxsize=None)
+def poolbwd_case(N, H2, W2, C_, ties):
+    """The layer below a max-pool at N x H2 x W2: raw output z, table, the gradient so far `base` (float32 [N,H2,W2,C]), the pooled gradient dP
+    [N,H2/2,W2/2,C], `first` (pool_argmax of the activated output, every window clear of rounding ties by its guard), the completed gradient
+    done = float32(base + pool_scatter_f64(dP, first)) -- a single fp32 add per element -- and its g.  ties: the BN scale row of channels 1 and
+    C - 2 is 0, so all four window values are equal there and the gradient belongs to window element 0.  The seed is the first of its
+    sequence for which the guards hold.  Read-only."""
+    seed0 = case_seed("poolbwd", N, H2, W2, C_, int(ties))
+    for seed in range(seed0, seed0 + 50):
+        gen = torch.Generator().manual_seed(seed)
+        z = torch.randn(N, H2, W2, C_, generator=gen) * 2 + 0.5
+        tab = bn_table(C_, seed + 3)
+        tied = torch.zeros(C_, dtype=torch.bool)
+        if ties:
+            tied[[1, C_ - 2]] = True
+            tab[L.BN_SCALE][tied] = 0.0
+        a, mag = _act64(z, tab[L.BN_SCALE], tab[L.BN_SHIFT])
+        try:
+            lrelu_slope(z.double(), tab[L.BN_SCALE].double(), tab[L.BN_SHIFT].double())
+            pool_argmax(a[..., ~tied], (3.0 * U24 * mag)[..., ~tied])
+        except AssertionError:
+            continue
+        break
+    else:
+        raise AssertionError("no seed clear of ties")
+    first = pool_argmax(a)
+    assert not ties or bool((first[..., tied] == 0).all())
+    base, dP = torch.randn(N, H2, W2, C_, generator=gen), torch.randn(N, H2 // 2, W2 // 2, C_, generator=gen)
+    done = (base + pool_scatter_f64(dP, first).float())
+    g64 = bwd_g_f64(z, done, tab)
+    val, bound = bwd_sums_f64(g64, z, tab)
+    return dict(z=z, tab=tab, base=base, dP=dP, first=first, done=done, a=a, g64=g64, val=val, bound=bound, seed=seed, tied=tied)
+
+
+def poolbwd_mutant(c, mutation):
+    """(completed gradient float32, sums [2][C]) of a poolbwd_case with one thing wrong.  last_max_wins: among equal maxima the last window
+    element takes the gradient; slope_from_dA_sign: see bwd_g_f64"""
+    first = c["first"]
+    if mutation == "last_max_wins":
+        w = pool_windows(c["a"])
+        first = torch.zeros_like(first)
+        for k in (1, 2, 3):
+            first = torch.where(w[k] == w.max(0).values, torch.full_like(first, k), first)
+    done = c["base"] + pool_scatter_f64(c["dP"], first).float()
+    g64 = bwd_g_f64(c["z"], done, c["tab"], mutation=mutation if mutation == "slope_from_dA_sign" else None)
+    return done, bwd_sums_f64(g64, c["z"], c["tab"])[0]
+
+
+# -- 6. hpfg_dropout_mask
+DROPMASK_N = (1, 255, 257, 100003, N_BIG_MIX)
+DROPMASK_P = (0.0, 0.3, 0.999)
+DROPMASK_SEED = 0xDEADBEEF
+DROPMASK_SEED_DEV = (0, 7, 0xFFFFFFFF)                      # seed + seed_dev wraps mod 2^32
