@@ -238,6 +238,9 @@ PROTOTYPES = {
     "hpfg_attn_window_drop_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _u32, _p, _p, _p]),
     "hpfg_attn_window_drop_elems": (_l, [_i, _i, _i, _i, _i]),
     "hpfg_attn_window_drop_mask": (_i, [_p, _i, _i, _i, _i, _i, _f, _u32, _p, _p]),
+    "hpfg_attn_window_packed_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _u32, _p, _p, _p]),
+    "hpfg_attn_window_packed_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _u32, _p, _p, _p]),
+    "hpfg_attn_window_packed_scratch_floats": (_l, [_i, _i, _i, _i, _i, _i, _i]),
     "hpfg_gelu_fwd": (_i, [_p, _p, _l, _p]),
     "hpfg_gelu_bwd": (_i, [_p, _p, _p, _l, _p]),
     "hpfg_token_dropout": (_i, [_p, _p, _l, _f, _u32, _p, _p, _p]),

@@ -9,6 +9,9 @@ reference.  Where the work runs, forward and backward, all through ``hpfg_amd.op
   the shifted-window mask.  The reference's roll / window partition / window reverse / roll back are the kernel's addressing -- no copy of
   qkv or of the output is made -- and because the proj Linear acts per token it commutes with window reverse and the roll back, so it is
   applied to the un-partitioned map;
+* ``window_attention_packed`` (``csrc/attn_window_packed.hip``) instead, where a module is built with the keyword-only ``packed=True``
+  (windows 2 .. 4 only): 64 // w^2 windows share one 64-row tile.  Same bias, mask and dropout elements; the LIDC factory of
+  ``model/swinunet.py`` sets it per stage from measurements, everything else leaves the default ``False`` and runs the kernels it ran before;
 * ``layer_norm``, ``linear`` (qkv, proj, fc1, fc2, reduction), ``gelu``, ``residual_scale`` (the residual add with its drop-path factor),
   ``patch_merge`` (the 2 x 2 gather of PatchMerging and its scatter backward).
 
@@ -22,8 +25,8 @@ encoder / decoder of ``model/swinunet.py`` do: ``attn_drop`` then runs inside th
 block, a stage and a network in turn, so that no two sites under one module share one) and draws keep(e) = hash(e, layer seed + seed word);
 the forward's own copy of the network's seed word and, for tests, explicit masks come in as a ``DropState``.  A block or stage used on its
 own has no seed word: its sites differ from each other, but every forward repeats the same masks -- the word, its advance and the
-per-instance base seed belong to the networks of ``model/swinunet.py``.  Eval mode launches no dropout.  ``build_model`` still refuses
-"swinunet".
+per-instance base seed belong to the networks of ``model/swinunet.py``.  Eval mode launches no dropout.  ``build_model`` opens
+"swinunet_plus" and "swinunet_lidc" and still refuses "swinunet".
 """
 from __future__ import annotations
 
@@ -32,7 +35,8 @@ import functools
 import torch
 import torch.nn as nn
 
-from ..ops_tokens import gelu, layer_norm, linear, patch_merge, residual_scale, token_dropout, window_attention, window_attention_dropout
+from ..ops_tokens import (MAX_PACKED_WINDOW, gelu, layer_norm, linear, patch_merge, residual_scale, token_dropout, window_attention,
+                          window_attention_dropout, window_attention_packed)
 
 
 def _no_dropout(who: str, allow: bool = False, **rates) -> None:
@@ -136,9 +140,12 @@ class Mlp(nn.Module):
 
 class WindowAttention(nn.Module):
     def __init__(self, dim: int, window_size: int, num_heads: int, qkv_bias: bool = True, attn_drop: float = 0., proj_drop: float = 0.,
-                 shift: bool = False, *, allow_dropout: bool = False):
+                 shift: bool = False, *, allow_dropout: bool = False, packed: bool = False):
         super().__init__()
         _no_dropout("WindowAttention", allow_dropout, attn_drop=attn_drop, proj_drop=proj_drop)
+        if packed and not 2 <= window_size <= MAX_PACKED_WINDOW:
+            raise ValueError(f"WindowAttention: packed=True is for windows 2 .. {MAX_PACKED_WINDOW} (csrc/attn_window_packed.hip), got {window_size}")
+        self.packed = bool(packed)          # which kernel family runs: chosen once, here, never in a launch path
         self.attn_drop, self.proj_drop = float(attn_drop), float(proj_drop)
         self.drop_seeds = (site_seed(0), site_seed(1))          # attn_drop, proj_drop; an enclosing block / stage / network numbers its sites anew
         self.window_size = window_size
@@ -159,7 +166,12 @@ class WindowAttention(nn.Module):
 
     def forward(self, x, drop: DropState = NO_DROP):
         qkv = linear(x, self.qkv.weight, self.qkv.bias)
-        if self.attn_drop == 0.0 or not self.training:
+        if self.packed:
+            on = self.attn_drop != 0.0 and self.training
+            a = window_attention_packed(qkv, self.relative_position_bias_table, self.num_heads, self.window_size, self.shift_size, self.scale,
+                                        self.attn_drop if on else 0.0, self.drop_seeds[0], drop.word if on else None,
+                                        drop.mask("attn_drop", qkv) if on else None)
+        elif self.attn_drop == 0.0 or not self.training:
             a = window_attention(qkv, self.relative_position_bias_table, self.num_heads, self.window_size, self.shift_size, self.scale)
         else:          # the mask is in the reference's attn layout [B nW, heads, L, L] (rolled, window-partitioned order)
             a = window_attention_dropout(qkv, self.relative_position_bias_table, self.num_heads, self.window_size, self.shift_size, self.scale,
@@ -171,13 +183,13 @@ class WindowAttention(nn.Module):
 
 class SwinTransformerBlock(nn.Module):
     def __init__(self, dim, num_heads, window_size=7, shift=False, mlp_ratio=4., qkv_bias=True, drop=0., attn_drop=0., drop_path=0.,
-                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, *, allow_dropout: bool = False):
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, *, allow_dropout: bool = False, packed: bool = False):
         super().__init__()
         _only("SwinTransformerBlock", "norm_layer", norm_layer, nn.LayerNorm)
         _no_dropout("SwinTransformerBlock", allow_dropout, drop=drop, attn_drop=attn_drop)
         self.norm1 = norm_layer(dim)
         self.attn = WindowAttention(dim, window_size=window_size, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop, shift=shift,
-                                    allow_dropout=allow_dropout)
+                                    allow_dropout=allow_dropout, packed=packed)
         self.dpr = float(drop_path)
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop, allow_dropout=allow_dropout)
@@ -209,7 +221,7 @@ class SwinTransformerBlock(nn.Module):
 class BasicBlock(nn.Module):
     def __init__(self, index: int, embed_dim: int = 96, window_size: int = 7, depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24),
                  mlp_ratio: float = 4., qkv_bias: bool = True, drop_rate: float = 0., attn_drop_rate: float = 0., drop_path: float = 0.1,
-                 norm_layer=nn.LayerNorm, patch_merging: bool = True, *, allow_dropout: bool = False):
+                 norm_layer=nn.LayerNorm, patch_merging: bool = True, *, allow_dropout: bool = False, packed: bool = False):
         super().__init__()
         depth = depths[index]
         dim = embed_dim * 2 ** index
@@ -217,7 +229,8 @@ class BasicBlock(nn.Module):
         rates = dpr[sum(depths[:index]):sum(depths[:index + 1])]
         self.blocks = nn.ModuleList([
             SwinTransformerBlock(dim=dim, num_heads=num_heads[index], window_size=window_size, shift=i % 2 == 1, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
-                                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=rates[i], norm_layer=norm_layer, allow_dropout=allow_dropout)
+                                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=rates[i], norm_layer=norm_layer, allow_dropout=allow_dropout,
+                                 packed=packed)
             for i in range(depth)])
         self.downsample = PatchMerging(dim=dim, norm_layer=norm_layer) if patch_merging else None
         self.external_draws = None        # one (attention, MLP) pair of [B] draws per block

@@ -1,11 +1,12 @@
 """The Swin-UNet of the reference (model/swinunet.py:27-49 PatchEmbedding, :85-111 PatchExpanding / FinalPatchExpanding, :333-379 BasicBlockUp,
-:382-536 encoder / decoder, :575-717 SwinUnet / SwinUnet_Plus, :720-778 the factories) assembled from the Swin blocks of ``model/swin.py`` on
+:382-536 encoder / decoder, :575-717 SwinUnet / SwinUnet_Plus, :720-778 the factories; model/swinunet_LIDC.py: the same network with
+``patch_size`` handed down to the final patch expanding, and ``get_swinunet_LIDC``) assembled from the Swin blocks of ``model/swin.py`` on
 the HIP token kernels.  Same constructor signatures, construction order, ``state_dict`` keys and ``init_weights`` pass as the reference, so a
 seed gives the reference's weights.
 
 Where the work runs (all through ``hpfg_amd.ops_tokens``; tokens stay an NHWC map):
-* patch embedding: kernel == stride, so the NCHW image is reshaped to [B, H/4, W/4, Cin * 16] (torch plumbing on the smallest tensor) and
-  goes through ``linear``;
+* patch embedding: kernel == stride, so the NCHW image is reshaped to [B, H/p, W/p, Cin * p^2] (p = patch_size: 4, or 2 in the LIDC network;
+  torch plumbing on the smallest tensor) and goes through ``linear``;
 * patch expanding: ``linear`` then ``expand_layer_norm`` -- the pixel shuffle is the LayerNorm kernel's row map, so the expanded tensor (the
   network's largest: [B,224,224,96] after the final one) is written once instead of copied and then normalised;
 * the skip connection: ``torch.cat`` + ``linear``; the head: ``linear`` with the prediction rows padded to a multiple of four, returned as
@@ -30,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from .. import heads
-from ..ops_tokens import expand_layer_norm, linear, seed_word_add
+from ..ops_tokens import LN_PX_FACTORS, expand_layer_norm, linear, seed_word_add
 from .swin import NO_DROP, BasicBlock, DropState, SwinTransformerBlock, _only, assign_site_seeds, dropout, norm, site_seed
 from .unet import _fresh_dropout_seed, _neck
 
@@ -73,20 +74,21 @@ class PatchExpanding(_Expanding):
 
 
 class FinalPatchExpanding(_Expanding):
-    factor = 4
-
-    def __init__(self, dim: int, norm_layer=nn.LayerNorm):
+    def __init__(self, dim: int, norm_layer=nn.LayerNorm, patch_size: int = 4):
         super().__init__()
         _only("FinalPatchExpanding", "norm_layer", norm_layer, nn.LayerNorm)
+        if patch_size not in LN_PX_FACTORS:
+            raise ValueError(f"FinalPatchExpanding: patch_size {patch_size} is not built; expand_layer_norm has the factors {LN_PX_FACTORS}")
         self.dim = dim
-        self.expand = nn.Linear(dim, 16 * dim, bias=False)
+        self.patch_size = self.factor = patch_size          # reference model/swinunet_LIDC.py:101-111 (4 in model/swinunet.py)
+        self.expand = nn.Linear(dim, patch_size ** 2 * dim, bias=False)
         self.norm = norm_layer(dim)
 
 
 class BasicBlockUp(nn.Module):
     def __init__(self, index: int, embed_dim: int = 96, window_size: int = 7, depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24),
                  mlp_ratio: float = 4., qkv_bias: bool = True, drop_rate: float = 0., attn_drop_rate: float = 0., drop_path: float = 0.1,
-                 patch_expanding: bool = True, norm_layer=nn.LayerNorm, *, allow_dropout: bool = False):
+                 patch_expanding: bool = True, norm_layer=nn.LayerNorm, *, allow_dropout: bool = False, packed: bool = False):
         super().__init__()
         index = len(depths) - index - 2          # the mirrored encoder stage: its depth, width, heads and drop-path slice (swinunet.py:348-354)
         depth = depths[index]
@@ -95,7 +97,8 @@ class BasicBlockUp(nn.Module):
         rates = dpr[sum(depths[:index]):sum(depths[:index + 1])]
         self.blocks = nn.ModuleList([
             SwinTransformerBlock(dim=dim, num_heads=num_heads[index], window_size=window_size, shift=i % 2 == 1, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias,
-                                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=rates[i], norm_layer=norm_layer, allow_dropout=allow_dropout)
+                                 drop=drop_rate, attn_drop=attn_drop_rate, drop_path=rates[i], norm_layer=norm_layer, allow_dropout=allow_dropout,
+                                 packed=packed)
             for i in range(depth)])
         self.upsample = PatchExpanding(dim=dim, norm_layer=norm_layer) if patch_expanding else nn.Identity()
         self.external_draws = None        # one (attention, MLP) pair of [B] draws per block
@@ -106,6 +109,17 @@ class BasicBlockUp(nn.Module):
         for i, layer in enumerate(self.blocks):
             x = layer(x, None if draws is None else draws[i], drop.sub(f"blocks.{i}"))
         return self.upsample(x)
+
+
+def _per_stage(packed, stages: int) -> tuple:
+    """``packed`` of the encoder / decoder / network constructors as one flag per encoder stage: a bool for all, or a sequence of ``stages``
+    bools (stage i of the encoder and the decoder stage that mirrors it run the same map size, so they share the flag)."""
+    if isinstance(packed, bool):
+        return (packed,) * stages
+    packed = tuple(bool(f) for f in packed)
+    if len(packed) != stages:
+        raise ValueError(f"packed {packed} must be a bool or one flag per stage ({stages})")
+    return packed
 
 
 def _stage_draws(draws, layers):
@@ -122,16 +136,17 @@ def _stage_draws(draws, layers):
 class SwinUnetEncoder(nn.Module):
     def __init__(self, patch_size: int = 4, in_chans: int = 3, embed_dim: int = 96, window_size: int = 7, depths: tuple = (2, 2, 6, 2),
                  num_heads: tuple = (3, 6, 12, 24), mlp_ratio: float = 4., qkv_bias: bool = True, drop_rate: float = 0., attn_drop_rate: float = 0.,
-                 drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True):
+                 drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True, *, packed=False):
         super().__init__()
         self.num_layers = len(depths)
+        packed = _per_stage(packed, len(depths))
         self.patch_embed = PatchEmbedding(patch_size=patch_size, in_c=in_chans, embed_dim=embed_dim, norm_layer=norm_layer if patch_norm else None)
         self.drop_rate = float(drop_rate)
         self.pos_drop_seed = site_seed(4)
         self.layers = nn.ModuleList([
             BasicBlock(index=i, depths=depths, embed_dim=embed_dim, num_heads=num_heads, drop_path=drop_path_rate, window_size=window_size,
                        mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, norm_layer=norm_layer,
-                       patch_merging=i != len(depths) - 1, allow_dropout=True)
+                       patch_merging=i != len(depths) - 1, allow_dropout=True, packed=packed[i])
             for i in range(len(depths))])
 
     def forward(self, x, drop: DropState = NO_DROP, draws=None):
@@ -150,20 +165,22 @@ class SwinUnetEncoder(nn.Module):
 class SwinUnetDecoder(nn.Module):
     def __init__(self, num_classes: int = 1000, embed_dim: int = 96, window_size: int = 7, depths: tuple = (2, 2, 6, 2),
                  num_heads: tuple = (3, 6, 12, 24), mlp_ratio: float = 4., qkv_bias: bool = True, drop_rate: float = 0., attn_drop_rate: float = 0.,
-                 drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm):
+                 drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_size: int = 4, *, packed=False):
         super().__init__()
         _only("SwinUnetDecoder", "norm_layer", norm_layer, nn.LayerNorm)
         n = len(depths)
+        packed = _per_stage(packed, n)
+        self.patch_size = patch_size
         self.num_layers = n
         self.first_patch_expanding = PatchExpanding(dim=embed_dim * 2 ** (n - 1), norm_layer=norm_layer)
         self.layers_up = nn.ModuleList([
             BasicBlockUp(index=i, depths=depths, embed_dim=embed_dim, num_heads=num_heads, drop_path=drop_path_rate, window_size=window_size,
                          mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, patch_expanding=i < n - 2,
-                         norm_layer=norm_layer, allow_dropout=True)
+                         norm_layer=norm_layer, allow_dropout=True, packed=packed[n - 2 - i])
             for i in range(n - 1)])
         self.skip_connection_layers = nn.ModuleList([nn.Linear(embed_dim * 2 ** (n - 2 - i) * 2, embed_dim * 2 ** (n - 2 - i)) for i in range(n - 1)])
         self.norm_up = norm_layer(embed_dim)
-        self.final_patch_expanding = FinalPatchExpanding(dim=embed_dim, norm_layer=norm_layer)
+        self.final_patch_expanding = FinalPatchExpanding(dim=embed_dim, norm_layer=norm_layer, patch_size=patch_size)
         self.head = nn.Conv2d(in_channels=embed_dim, out_channels=num_classes, kernel_size=(1, 1), bias=False)
 
     def forward(self, feats, drop: DropState = NO_DROP, draws=None):
@@ -193,14 +210,14 @@ def _init_weights(m):
 class SwinUnet(nn.Module):
     def __init__(self, patch_size: int = 4, in_chans: int = 3, num_classes: int = 1000, embed_dim: int = 96, window_size: int = 7,
                  depths: tuple = (2, 2, 6, 2), num_heads: tuple = (3, 6, 12, 24), mlp_ratio: float = 4., qkv_bias: bool = True, drop_rate: float = 0.,
-                 attn_drop_rate: float = 0., drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True):
+                 attn_drop_rate: float = 0., drop_path_rate: float = 0.1, norm_layer=nn.LayerNorm, patch_norm: bool = True, *, packed=False):
         super().__init__()
         self.encoder = SwinUnetEncoder(patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim, window_size=window_size, depths=depths,
                                        num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
-                                       drop_path_rate=drop_path_rate, norm_layer=norm_layer, patch_norm=patch_norm)
+                                       drop_path_rate=drop_path_rate, norm_layer=norm_layer, patch_norm=patch_norm, packed=packed)
         self.decoder = SwinUnetDecoder(num_classes=num_classes, embed_dim=embed_dim, window_size=window_size, depths=depths, num_heads=num_heads,
                                        mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
-                                       drop_path_rate=drop_path_rate, norm_layer=norm_layer)
+                                       drop_path_rate=drop_path_rate, norm_layer=norm_layer, patch_size=patch_size, packed=packed)
         self._build_necks(embed_dim * 2 ** (len(depths) - 1), num_classes)
         self.apply(self.init_weights)          # the necks' nn.Linear layers included, as the reference's apply does
         self.has_dropout = drop_rate > 0.0 or attn_drop_rate > 0.0
@@ -299,3 +316,25 @@ def get_swinunet(img_size: int = 224, patch_size: int = 4, in_channels: int = 3,
 
 def get_swinunet_plus(img_size: int = 224, patch_size: int = 4, in_channels: int = 3, num_classes: int = 4):
     return _factory(SwinUnet_Plus, img_size, patch_size, in_channels, num_classes)
+
+
+# Which encoder stages (and the decoder stages that mirror them) of the LIDC network run the packed small-window kernels, by window.  The rule
+# (profiles/swinunet_lidc_timing.txt): a stage keeps ``packed`` only where the measured (min .. max) range of the packed forward + backward
+# pair lies wholly below the unpacked pair's at the configuration's batch; the choice is made here, at construction, never in a launch path.
+# Measured at batch 64: window 3 (96 x 96) packed 0.22 / 0.27 / 0.35 / 0.54 of the unpacked pair on the 48 / 24 / 12 / 6 maps; window 4 (64 x 64)
+# 0.38 / 0.44 / 0.86 on the 32 / 16 / 8 maps, and on the 4 x 4 map -- one window per image, as many workgroups either way -- the ranges overlap.
+LIDC_PACKED = {3: (True, True, True, True), 4: (True, True, True, False)}
+
+
+def get_swinunet_LIDC(img_size: int = 96, patch_size: int = 2, in_channels: int = 3, num_classes: int = 4):
+    """The reference's LIDC Swin-UNet (model/swinunet_LIDC.py:619-646): patch 2, window 3 at 96 x 96 (token maps 48 / 24 / 12 / 6) or window 4
+    at 64 x 64 (32 / 16 / 8 / 4), otherwise the rates and depths of ``get_swinunet``."""
+    if img_size == 96:
+        window_size = 3
+    elif img_size == 64:
+        window_size = 4
+    else:
+        raise NotImplementedError(f"get_swinunet_LIDC: image side {img_size} is not built (96: window 3, 64: window 4)")
+    return SwinUnet(patch_size=patch_size, in_chans=in_channels, num_classes=num_classes, embed_dim=96, window_size=window_size, depths=(2, 2, 6, 2),
+                    num_heads=(3, 6, 12, 24), mlp_ratio=4., qkv_bias=True, drop_rate=0.1, attn_drop_rate=0.1, drop_path_rate=0.2,
+                    norm_layer=partial(nn.LayerNorm, eps=1e-6), packed=LIDC_PACKED[window_size])

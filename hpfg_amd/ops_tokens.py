@@ -1,5 +1,5 @@
 """Autograd bindings of the token-layout HIP kernels (csrc/tokens.hip) used by the SegFormer branch: LayerNorm, the attention core
-softmax(q k^T) v, depthwise-3x3 + GELU, and the shifted-window attention, GELU and patch merging of the Swin blocks (csrc/attn_window.hip), and the window mask, mask-token substitution and masked loss of the Swin-MAE pretraining (csrc/mae.hip).  Device tensors only; the library raises if it is missing (no fallback)."""
+softmax(q k^T) v, depthwise-3x3 + GELU, and the shifted-window attention, GELU and patch merging of the Swin blocks (csrc/attn_window.hip; csrc/attn_window_packed.hip for windows of at most 16 tokens), and the window mask, mask-token substitution and masked loss of the Swin-MAE pretraining (csrc/mae.hip).  Device tensors only; the library raises if it is missing (no fallback)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -439,6 +439,61 @@ def window_attention_dropout(qkv: torch.Tensor, bias_table: torch.Tensor, heads:
         return window_attention(qkv, bias_table, heads, window, shift, scale)
     _window_args("window_attention_dropout", qkv, bias_table, heads, window, shift)
     return _WindowAttentionDrop.apply(qkv, bias_table, int(heads), int(window), int(shift), float(scale), float(p), int(seed) & 0xFFFFFFFF, seed_dev, mask)
+
+
+MAX_PACKED_WINDOW = 4          # csrc/attn_window_packed.hip: windows of at most 16 tokens, 64 // window^2 of them per tile
+
+
+class _WindowAttentionPacked(torch.autograd.Function):
+    """_WindowAttentionDrop on the packed small-window kernels (hpfg_attn_window_packed_fwd / _bwd); p = 0 without a mask is their
+    no-dropout form."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias_table, heads, window, shift, scale, p, seed, seed_dev, mask):
+        lib = L.load()
+        qc, tc = qkv.contiguous().float(), bias_table.contiguous().float()
+        B, H, W, C3 = qc.shape
+        d = C3 // 3 // heads
+        out = torch.empty(B, H, W, C3 // 3, dtype=torch.float32, device=qkv.device)
+        ctx.math = _MATH_CODE[gemm_math()]
+        L.check(lib.hpfg_attn_window_packed_fwd(L.ptr(qc), L.ptr(tc), L.ptr(out), B, H, W, heads, d, window, shift, scale, ctx.math, p, seed,
+                                                L.ptr(seed_dev), L.ptr(mask), _st(qkv)), "attn_window_packed_fwd")
+        ctx.save_for_backward(qc, tc)
+        ctx.geo = (heads, d, window, shift, scale)
+        ctx.drop = (p, seed, seed_dev, mask)          # seed_dev is the forward's own copy of the seed word
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        qkv, table = ctx.saved_tensors
+        heads, d, window, shift, scale = ctx.geo
+        p, seed, seed_dev, mask = ctx.drop
+        B, H, W, _ = qkv.shape
+        do = dout.contiguous()
+        dqkv, dtable = torch.empty_like(qkv), torch.empty_like(table)
+        n_scr = lib.hpfg_attn_window_packed_scratch_floats(B, H, W, heads, d, window, ctx.math)
+        if n_scr < 0:
+            L.check(-1, "attn_window_packed_scratch_floats")
+        scratch = torch.empty(n_scr, dtype=torch.float32, device=qkv.device)
+        L.check(lib.hpfg_attn_window_packed_bwd(L.ptr(qkv), L.ptr(table), L.ptr(do), L.ptr(dqkv), L.ptr(dtable), L.ptr(scratch), B, H, W, heads, d, window,
+                                                shift, scale, ctx.math, p, seed, L.ptr(seed_dev), L.ptr(mask), _st(qkv)), "attn_window_packed_bwd")
+        return dqkv, dtable, None, None, None, None, None, None, None, None
+
+
+def window_attention_packed(qkv: torch.Tensor, bias_table: torch.Tensor, heads: int, window: int, shift: int, scale: float, p: float = 0.0, seed: int = 0,
+                            seed_dev=None, mask=None) -> torch.Tensor:
+    """``window_attention`` / ``window_attention_dropout`` for windows of at most MAX_PACKED_WINDOW = 4 tokens a side on the packed kernels
+    (csrc/attn_window_packed.hip): 64 // window^2 windows share one 64-row tile instead of one padded tile per window.  Same arguments, same
+    result up to the rounding of a differently ordered softmax sum (equal bits in HPFG_MATH_F32), same dropout elements, so
+    ``window_attention_drop_mask`` and a mask recorded from the reference serve both.  p = 0 without a mask is the no-dropout form."""
+    if not 2 <= window <= MAX_PACKED_WINDOW:
+        raise ValueError(f"window_attention_packed: window {window} is outside 2 .. {MAX_PACKED_WINDOW}: the packed kernels take windows of at most "
+                         f"{MAX_PACKED_WINDOW} x {MAX_PACKED_WINDOW} = {MAX_PACKED_WINDOW ** 2} tokens (larger windows: window_attention)")
+    _window_args("window_attention_packed", qkv, bias_table, heads, window, shift)
+    B, H, W, _ = qkv.shape
+    _drop_args("window_attention_packed", p, seed_dev, mask, window_attention_mask_elems(B, H, W, heads, window))
+    return _WindowAttentionPacked.apply(qkv, bias_table, int(heads), int(window), int(shift), float(scale), float(p), int(seed) & 0xFFFFFFFF, seed_dev, mask)
 
 
 def window_attention_drop_mask(B: int, H: int, W: int, heads: int, window: int, p: float, seed: int, seed_dev=None, device="cuda") -> torch.Tensor:

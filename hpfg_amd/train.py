@@ -304,7 +304,16 @@ class _StepBase:
 
 
 class SupervisedStep(_StepBase):
+    """sup_ACDC.py:83-93: forward, 0.5 (CE + Dice), backward, update.  A U-Net brings its flat buffers; a
+    Swin-UNet (``get_swinunet_LIDC``) is laid into one flat parameter buffer here, as HPFGStep does for its token networks, so that its
+    optimizer step is one kernel whatever ``args.opt`` is.  Its dropout is counter-based (a captured step draws new masks per replay from the
+    seed word) and its drop-path draws from torch's device generator."""
+
     def __init__(self, model, args, dp=None):
+        from .model.swinunet import SwinUnet
+        from .utils.optim import flatten_parameters
+        if isinstance(model, SwinUnet):
+            flatten_parameters(model)
         super().__init__(args, dp, [model])
         self.sc.host[S_COEF_A:S_COEF_A + 2] = torch.tensor([0.5, 0.5])
 

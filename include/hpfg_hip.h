@@ -660,6 +660,26 @@ int hpfg_attn_window_drop_bwd(const float* qkv, const float* bias_table, const f
 long hpfg_attn_window_drop_elems(int B, int H, int W, int heads, int window);
 int hpfg_attn_window_drop_mask(uint8_t* out, int B, int H, int W, int heads, int window, float p, uint32_t seed, const uint32_t* seed_dev, void* stream);
 
+/* ---- the same attention for windows of at most 16 tokens, several windows per 64-row tile (csrc/attn_window_packed.hip) ------------------- */
+/* The operation of hpfg_attn_window_drop_fwd (reference model/swinunet.py:219-241 with the roll / window partition / window reverse / roll
+ * back of :263-276; the LIDC network of model/swinunet_LIDC.py runs it at window 3 and 4) for window 2, 3 or 4: 64 / window^2 windows of one
+ * (image, head), in raster order, share a workgroup's tile; keys of another window of the tile are excluded exactly, like padding keys.
+ * Same tensors, same bias and mask, same dropout elements (win = the window's index in the image), so hpfg_attn_window_drop_mask /
+ * _drop_elems serve both.  p == 0 with a null mask is the no-dropout form.  HPFG_MATH_F32 runs the kernels of hpfg_attn_window_drop_fwd
+ * (equal bits).  Returns -1 with hpfg_last_error naming the rule: window outside 2 .. 4, a side that is no multiple of the window, a shift
+ * that is neither 0 nor window / 2, a head dim other than 32 / 64, a null pointer. */
+int hpfg_attn_window_packed_fwd(const float* qkv, const float* bias_table, float* out, int B, int H, int W, int heads, int head_dim, int window, int shift,
+                                float scale, int math, float p, uint32_t seed, const uint32_t* seed_dev, const uint8_t* mask, void* stream);
+/* Backward of the above (the same reference lines under autograd): every element of dqkv written exactly once; dbias from per-workgroup
+ * partials added in a fixed order (no atomics: two runs give the same bits).  scratch: hpfg_attn_window_packed_scratch_floats(...) floats,
+ * every one of them written. */
+int hpfg_attn_window_packed_bwd(const float* qkv, const float* bias_table, const float* dout, float* dqkv, float* dbias, float* scratch, int B, int H,
+                                int W, int heads, int head_dim, int window, int shift, float scale, int math, float p, uint32_t seed,
+                                const uint32_t* seed_dev, const uint8_t* mask, void* stream);
+/* Floats of that scratch (reference model/swinunet.py:207-248 needs none: autograd scatter-adds into the table): one [heads][(2 window - 1)^2]
+ * slab per (image, tile) in HPFG_MATH_BF16X3, hpfg_attn_window_scratch_floats in HPFG_MATH_F32; -1 with hpfg_last_error set for a refused shape. */
+long hpfg_attn_window_packed_scratch_floats(int B, int H, int W, int heads, int head_dim, int window, int math);
+
 /* ---- Swin-MAE pretraining (csrc/mae.hip; reference model/swin_mae.py, 2022_12_CVPR_Swin-MAE.py) ------------------------------------------ */
 /* window_masking with remove=False, mask_len_sparse=False (reference model/swin_mae.py:649-710) from a given noise tensor: the S x S token map
  * is cut into d x d groups of r x r tokens (d = S / r); a group is kept iff its rank among the image's d * d noise values, ascending by
