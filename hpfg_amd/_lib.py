@@ -19,7 +19,7 @@ OPT_CONV_THIN, OPT_FIRST_MFMA, OPT_FIRST_WGRAD, OPT_NARROW_DEEP, OPT_UPDATE_PACK
 LOSS_NSUM = 32              # C <= 4; hpfg_loss_nsum(C) is the length for any supported C
 LOSS_MAX_CLASSES = 16
 ACC_MAX_SHARDS = 8          # HPFG_ACC_MAX_SHARDS: a BatchNorm sum accumulator is long long [shards][2][C][2]
-VERSION = 143
+VERSION = 144
 RESIZE_TAPS = 36            # HPFG_RESIZE_TAPS: coefficients per output sample and axis of hpfg_resize_cubic's tap tables
 SURFACE_SEGS = 32           # HPFG_SURFACE_SEGS: surface-point segments of hpfg_surface_*, (class - 1) * 2 + side (0 = pred, 1 = gt)
 MATH_F32, MATH_BF16X3 = 0, 1
@@ -201,6 +201,12 @@ PROTOTYPES = {
     "hpfg_tok_stat_blocks": (_i, [_l]),
     "hpfg_bnrelu_apply": (_i, [_p, _p, _p, _p, _p, _p, _f, _l, _p, _l, _i, _p]),
     "hpfg_bnrelu_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _f, _l, _p, _p, _p, _l, _i, _p]),
+    "hpfg_dwconv_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "hpfg_dwconv_bwd": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "hpfg_dwconv_bwd_blocks": (_i, [_i, _i, _i, _i]),
+    "hpfg_bn_tok_stats": (_i, [_p, _l, _i, _p, _p, _p]),
+    "hpfg_bn_tok_apply": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p]),
+    "hpfg_bn_tok_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "hpfg_noise_add": (_i, [_p, _p, _p, _l, _l, _f, _f, _f, _p]),
     "hpfg_uncertainty_mask": (_i, [C.POINTER(PredBlocks), _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "hpfg_mix_samples": (_i, [_p, _p, _p, _p, _i, _l, _p]),

@@ -693,7 +693,9 @@ __global__ __launch_bounds__(64) void col_stats_finish_kernel(const float* __res
   }
 }
 
-// y = relu((x - mean) * rstd * gamma + beta) * mask[row / rows_per_image][c] * inv_keep
+// y = relu((x - mean) * rstd * gamma + beta) * mask[row / rows_per_image][c] * inv_keep; RELU = false (token BatchNorm alone, reference
+// model/uniformer.py CBlock.norm1 / norm2 :93,97 and the stage norms :292-295): y = (x - mean) * rstd * gamma + beta, mask and inv_keep unused
+template <bool RELU>
 __global__ __launch_bounds__(256) void bnrelu_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ mask, float inv_keep, long rows_per_image, float* __restrict__ y,
@@ -710,12 +712,16 @@ __global__ __launch_bounds__(256) void bnrelu_apply_kernel(const float* __restri
     if (mask) m = *reinterpret_cast<const f32x4*>(mask + (r / rows_per_image) * C + c) * inv_keep;
     f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = fmaxf((v[j] - mu[j]) * rs[j] * g[j] + be[j], 0.f) * (mask ? m[j] : 1.f);
+    for (int j = 0; j < 4; ++j) {
+      if (RELU) o[j] = fmaxf((v[j] - mu[j]) * rs[j] * g[j] + be[j], 0.f) * (mask ? m[j] : 1.f);
+      else o[j] = (v[j] - mu[j]) * rs[j] * g[j] + be[j];
+    }
     *reinterpret_cast<f32x4*>(y + r * C + c) = o;
   }
 }
 
-// backward sums: g = dy * mask * inv_keep * [bn(x) > 0];  part[blk][0] = sum g, part[blk][1] = sum g * xhat
+// backward sums: g = dy * mask * inv_keep * [bn(x) > 0] (RELU = false: g = dy);  part[blk][0] = sum g, part[blk][1] = sum g * xhat
+template <bool RELU>
 __global__ __launch_bounds__(256) void bnrelu_bwd_stats_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const float* __restrict__ mask, float inv_keep,
@@ -734,7 +740,7 @@ __global__ __launch_bounds__(256) void bnrelu_bwd_stats_kernel(const float* __re
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float xh = (v[j] - mu[j]) * rs[j];
-        const float g = xh * ga[j] + be[j] > 0.f ? d[j] * m[j] : 0.f;
+        const float g = RELU ? (xh * ga[j] + be[j] > 0.f ? d[j] * m[j] : 0.f) : d[j];
         a[j] += g;
         b[j] += g * xh;
       }
@@ -754,6 +760,7 @@ __global__ __launch_bounds__(256) void bnrelu_bwd_stats_kernel(const float* __re
 }
 
 // dx = gamma * rstd * (g - sum_g / R - xhat * sum_gx / R)
+template <bool RELU>
 __global__ __launch_bounds__(256) void bnrelu_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, const float* __restrict__ mask, float inv_keep,
@@ -775,7 +782,7 @@ __global__ __launch_bounds__(256) void bnrelu_bwd_apply_kernel(const float* __re
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float xh = (v[j] - mu[j]) * rs[j];
-      const float g = xh * ga[j] + be[j] > 0.f ? d[j] * m[j] : 0.f;
+      const float g = RELU ? (xh * ga[j] + be[j] > 0.f ? d[j] * m[j] : 0.f) : d[j];
       o[j] = ga[j] * rs[j] * (g - s1[j] * invR - xh * s2[j] * invR);
     }
     *reinterpret_cast<f32x4*>(dx + r * C + c) = o;
@@ -1149,7 +1156,7 @@ extern "C" int hpfg_tok_col_stats(const float* x, long R, int C, float* partials
 extern "C" int hpfg_bnrelu_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* mask,
                                  float inv_keep, long rows_per_image, float* y, long R, int C, void* stream) {
   HPFG_ARG_CHECK(x && mean && rstd && gamma && beta && y && R > 0 && C % 4 == 0 && C >= 4 && rows_per_image > 0, "bnrelu_apply: bad args");
-  hipLaunchKernelGGL(bnrelu_apply_kernel, dim3(grid_cap(R * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, mask,
+  hipLaunchKernelGGL(bnrelu_apply_kernel<true>, dim3(grid_cap(R * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, mask,
                      inv_keep, rows_per_image, y, R, C);
   return hpfg_launch_status("bnrelu_apply_kernel");
 }
@@ -1159,12 +1166,50 @@ extern "C" int hpfg_bnrelu_bwd(const float* x, const float* dy, const float* mea
                                void* stream) {
   HPFG_ARG_CHECK(x && dy && mean && rstd && gamma && beta && dx && partials && sums && R > 0 && tok_c_ok(C) && rows_per_image > 0, "bnrelu_bwd: bad args");
   const int nblk = hpfg_tok_stat_blocks(R);
-  hipLaunchKernelGGL(bnrelu_bwd_stats_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, dy, mean, rstd, gamma, beta, mask, inv_keep,
+  hipLaunchKernelGGL(bnrelu_bwd_stats_kernel<true>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, dy, mean, rstd, gamma, beta, mask, inv_keep,
                      rows_per_image, R, C, partials, (int)((R + nblk - 1) / nblk));
   hipLaunchKernelGGL(col_reduce_kernel, dim3(2 * C), dim3(64), 0, (hipStream_t)stream, partials, nblk, 2 * C, sums);
-  hipLaunchKernelGGL(bnrelu_bwd_apply_kernel, dim3(grid_cap(R * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, dy, mean, rstd, gamma, beta, mask,
+  hipLaunchKernelGGL(bnrelu_bwd_apply_kernel<true>, dim3(grid_cap(R * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, dy, mean, rstd, gamma, beta, mask,
                      inv_keep, rows_per_image, sums, dx, R, C);
   return hpfg_launch_status("bnrelu_bwd_kernel");
+}
+
+// ---- token BatchNorm without an activation (hpfg_bn_tok_*): the RELU = false instances of the kernels above --------------------------------------
+// Thread <-> (quad t % Q, row lane t / Q) leaves 256 % Q threads of a workgroup idle when Q does not divide 256 (C = 320: 16 of them); the
+// kernels guard for that (pl < PL), so every C % 4 == 0 up to 1024 is admitted here.  hpfg_tok_col_stats keeps its narrower contract.
+static int bn_tok_c_ok(int C) { return C % 4 == 0 && C >= 4 && C <= 1024; }
+
+extern "C" int hpfg_bn_tok_stats(const float* x, long R, int C, float* partials, float* sums, void* stream) {
+  HPFG_ARG_CHECK(x && partials && sums && R > 0 && bn_tok_c_ok(C), "bn_tok_stats: bad args (C %% 4 == 0, 4 <= C <= 1024; got R %ld C %d)", R, C);
+  const int nblk = hpfg_tok_stat_blocks(R);
+  const int per = (int)((R + nblk - 1) / nblk);
+  hipLaunchKernelGGL(col_stats_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, R, C, partials, per);
+  hipLaunchKernelGGL(col_stats_finish_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, partials, nblk, C, R, per, x, sums);
+  return hpfg_launch_status("col_stats_kernel");
+}
+
+extern "C" int hpfg_bn_tok_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y, long R, int C,
+                                 void* stream) {
+  HPFG_ARG_CHECK(x && mean && rstd && gamma && beta && y && R > 0 && bn_tok_c_ok(C), "bn_tok_apply: bad args (C %% 4 == 0, 4 <= C <= 1024; got R %ld C %d)",
+                 R, C);
+  const float* none = nullptr;
+  hipLaunchKernelGGL(bnrelu_apply_kernel<false>, dim3(grid_cap(R * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma, beta, none,
+                     1.f, 1L, y, R, C);
+  return hpfg_launch_status("bn_tok_apply_kernel");
+}
+
+extern "C" int hpfg_bn_tok_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma, float* dx, float* partials,
+                               float* sums, long R, int C, void* stream) {
+  HPFG_ARG_CHECK(x && dy && mean && rstd && gamma && dx && partials && sums && R > 0 && bn_tok_c_ok(C),
+                 "bn_tok_bwd: bad args (C %% 4 == 0, 4 <= C <= 1024; got R %ld C %d)", R, C);
+  const int nblk = hpfg_tok_stat_blocks(R);
+  const float* none = nullptr;
+  hipLaunchKernelGGL(bnrelu_bwd_stats_kernel<false>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, dy, mean, rstd, gamma, gamma, none, 1.f, 1L, R, C,
+                     partials, (int)((R + nblk - 1) / nblk));
+  hipLaunchKernelGGL(col_reduce_kernel, dim3(2 * C), dim3(64), 0, (hipStream_t)stream, partials, nblk, 2 * C, sums);
+  hipLaunchKernelGGL(bnrelu_bwd_apply_kernel<false>, dim3(grid_cap(R * (C / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, dy, mean, rstd, gamma, gamma,
+                     none, 1.f, 1L, sums, dx, R, C);
+  return hpfg_launch_status("bn_tok_bwd_kernel");
 }
 
 static void lw_tile(int N, int K, int& TN, int& TK) {

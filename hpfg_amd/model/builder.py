@@ -7,13 +7,16 @@ config/ccnet_swinunet_30k_224x224_ACDC.yaml; see model/swinunet.py; "swinunet" i
 get_swinunet_LIDC(img_size=train_crop_size[0] or train_crop_size) (the patch-2 Swin-UNet of the reference's model/swinunet_LIDC.py, window 3 at
 96 x 96 or 4 at 64 x 64, on the packed small-window attention kernels; the key of config/swinunet_30k_96x96_LIDC.yaml), "swinmae" ->
 swin_mae(in_channels, mask_ratio=args.mask_ratio) (the masked-autoencoder pretraining of the Swin encoder, the key of the reference's
-config/swinmae_30k_224x224_ACDC.yaml; see model/swin_mae.py).  Every other key of the reference's factory is outside this build's scope and
+config/swinmae_30k_224x224_ACDC.yaml; see model/swin_mae.py), "uniformer_plus" -> Uniformer_Plus (UniFormer-S + SegFormerHead + the projection
+necks, the key of the reference's config/ccnet_uniformer_30k_224x224_ACDC.yaml; square inputs with a side of 128 to 256, a multiple of 32;
+see model/uniformer.py).  Every other key of the reference's factory is outside this build's scope and
 raises NotImplementedError exactly like an unknown key does there (builder.py:59-60).
 """
 from .segformer import SegFormer, SegFormer_Plus
 from .swin_mae import swin_mae
 from .swinunet import get_swinunet_LIDC, get_swinunet_plus
 from .unet import UNet, UNet_Plus
+from .uniformer import Uniformer_Plus
 
 
 def build_model(args):
@@ -33,4 +36,6 @@ def build_model(args):
                                  num_classes=args.num_classes)
     if args.model == "swinmae":
         return swin_mae(in_channels=args.in_channels, mask_ratio=args.mask_ratio)
+    if args.model == "uniformer_plus":          # reference model/builder.py:57-58
+        return Uniformer_Plus(image_size=args.train_crop_size, in_channels=args.in_channels, num_classes=args.num_classes)
     raise NotImplementedError(f"model '{args.model}' is outside the MI355X hot-path build (see DESIGN.md, scope)")

@@ -595,6 +595,148 @@ def dwconv_gelu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> to
     return _DWGelu.apply(x, weight, bias)
 
 
+class _DWConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, k, residual, res_is_x):
+        lib = L.load()
+        xc = x.contiguous()
+        B, H, W, C_ = xc.shape
+        wk = weight.reshape(C_, k * k).t().contiguous()
+        res = xc if res_is_x else (None if residual is None else residual.contiguous())
+        y = torch.empty_like(xc)
+        L.check(lib.hpfg_dwconv_fwd(L.ptr(xc), L.ptr(wk), L.ptr(bias), L.ptr(res), L.ptr(y), B, H, W, C_, k, _st(x)), "dwconv_fwd")
+        ctx.save_for_backward(xc, wk)
+        ctx.k, ctx.wshape = k, weight.shape
+        ctx.res, ctx.res_is_x = residual is not None, res_is_x
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.load()
+        x, wk = ctx.saved_tensors
+        B, H, W, C_ = x.shape
+        k = ctx.k
+        dyc = dy.contiguous()
+        dx = torch.empty_like(x)
+        dwb = torch.empty(k * k + 1, C_, dtype=torch.float32, device=x.device)
+        part = torch.empty(lib.hpfg_dwconv_bwd_blocks(B, H, W, k) * (k * k + 1) * C_, dtype=torch.float32, device=x.device)
+        # x + dw(x): the residual's gradient is dy itself, added to dx inside the kernel
+        L.check(lib.hpfg_dwconv_bwd(L.ptr(x), L.ptr(wk), L.ptr(dyc), L.ptr(dx), 1 if ctx.res_is_x else 0, L.ptr(dwb), L.ptr(dwb[k * k]), L.ptr(part),
+                                    B, H, W, C_, k, _st(x)), "dwconv_bwd")
+        return dx, dwb[:k * k].t().reshape(ctx.wshape), dwb[k * k], None, dyc if ctx.res else None, None
+
+
+def dwconv(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, k: int, residual=None) -> torch.Tensor:
+    """residual + depthwise_conv_kxk(x) + bias on x [B,H,W,C] (NHWC), k = 3 or 5, padding k // 2; weight [C,1,k,k] as
+    nn.Conv2d(C, C, k, padding=k // 2, groups=C) holds it.  ``residual`` is None, x itself (x + dwconv(x): one gradient for both uses) or
+    another [B,H,W,C] tensor."""
+    _need_gpu(x, "dwconv")
+    if k not in (3, 5):
+        raise ValueError(f"dwconv: k must be 3 or 5 (got {k})")
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[3] % 4 != 0 or x.numel() == 0:
+        raise ValueError(f"dwconv: x must be a non-empty float32 [B,H,W,C] with C % 4 == 0 (got {tuple(x.shape)}, {x.dtype})")
+    C_ = x.shape[3]
+    if tuple(weight.shape) != (C_, 1, k, k) or tuple(bias.shape) != (C_,):
+        raise ValueError(f"dwconv: weight must be [{C_},1,{k},{k}] and bias [{C_}] (got {tuple(weight.shape)}, {tuple(bias.shape)})")
+    if residual is not None and (residual.shape != x.shape or residual.dtype != torch.float32):
+        raise ValueError(f"dwconv: residual must be a float32 tensor of x's shape {tuple(x.shape)} (got {tuple(residual.shape)}, {residual.dtype})")
+    return _DWConv.apply(x, weight, bias, k, None if residual is x else residual, residual is x)
+
+
+class _BNTokens(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        lib = L.load()
+        C_ = x.shape[-1]
+        xc = x.contiguous()
+        R = xc.numel() // C_
+        part = torch.empty(lib.hpfg_tok_stat_blocks(R) * 2 * C_, dtype=torch.float32, device=x.device)
+        sums = torch.empty(2, C_, dtype=torch.float32, device=x.device)
+        L.check(lib.hpfg_bn_tok_stats(L.ptr(xc), R, C_, L.ptr(part), L.ptr(sums), _st(x)), "bn_tok_stats")
+        mean = sums[0] / R
+        var = sums[1] / R          # centred squares: no E[x^2] - mean^2 to cancel
+        rstd = torch.rsqrt(var + eps)
+        y = torch.empty_like(xc)
+        L.check(lib.hpfg_bn_tok_apply(L.ptr(xc), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(beta), L.ptr(y), R, C_, _st(x)), "bn_tok_apply")
+        ctx.save_for_backward(xc, gamma, mean, rstd)
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, dy, _dm, _dv):
+        lib = L.load()
+        x, gamma, mean, rstd = ctx.saved_tensors
+        C_ = x.shape[-1]
+        R = x.numel() // C_
+        dyc = dy.contiguous()
+        dx = torch.empty_like(x)
+        part = torch.empty(lib.hpfg_tok_stat_blocks(R) * 2 * C_, dtype=torch.float32, device=x.device)
+        sums = torch.empty(2, C_, dtype=torch.float32, device=x.device)
+        L.check(lib.hpfg_bn_tok_bwd(L.ptr(x), L.ptr(dyc), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(dx), L.ptr(part), L.ptr(sums), R, C_, _st(x)),
+                "bn_tok_bwd")
+        return dx, sums[1], sums[0], None
+
+
+def batch_norm_tokens(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5):
+    """Train-mode BatchNorm over all tokens of x [..., C] (every leading axis is a batch axis), no activation.  Returns (y, batch mean, biased
+    batch variance); the caller updates the running statistics."""
+    _need_gpu(x, "batch_norm_tokens")
+    if x.dim() < 2 or x.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError(f"batch_norm_tokens: x must be a non-empty float32 [..., C] (got {tuple(x.shape)}, {x.dtype})")
+    C_ = x.shape[-1]
+    if C_ % 4 != 0 or C_ > 1024:
+        raise ValueError(f"batch_norm_tokens: C must be a multiple of 4, at most 1024 (got {C_})")
+    if tuple(gamma.shape) != (C_,) or tuple(beta.shape) != (C_,):
+        raise ValueError(f"batch_norm_tokens: gamma and beta must be [{C_}] (got {tuple(gamma.shape)}, {tuple(beta.shape)})")
+    if not eps > 0.0:
+        raise ValueError(f"batch_norm_tokens: eps must be positive (got {eps})")
+    return _BNTokens.apply(x, gamma, beta, eps)
+
+
+class _BNTokensEval(torch.autograd.Function):
+    """y = (x - running_mean) * rstd * gamma + beta with fixed statistics.  Backward: dbeta = sum dy and dgamma = sum dy xhat are the sums of
+    hpfg_bn_tok_bwd (its dx, the train-mode formula, is discarded); dx = dy * rstd * gamma is the apply kernel on dy with mean 0, beta 0."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, mean, rstd):
+        C_ = x.shape[-1]
+        xc = x.contiguous()
+        y = torch.empty_like(xc)
+        L.check(L.load().hpfg_bn_tok_apply(L.ptr(xc), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(beta), L.ptr(y), xc.numel() // C_, C_, _st(x)),
+                "bn_tok_apply")
+        ctx.save_for_backward(xc, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.load()
+        x, gamma, mean, rstd = ctx.saved_tensors
+        C_ = x.shape[-1]
+        R = x.numel() // C_
+        dyc = dy.contiguous()
+        dx, scratch = torch.empty_like(x), torch.empty_like(x)
+        part = torch.empty(lib.hpfg_tok_stat_blocks(R) * 2 * C_, dtype=torch.float32, device=x.device)
+        sums = torch.empty(2, C_, dtype=torch.float32, device=x.device)
+        L.check(lib.hpfg_bn_tok_bwd(L.ptr(x), L.ptr(dyc), L.ptr(mean), L.ptr(rstd), L.ptr(gamma), L.ptr(scratch), L.ptr(part), L.ptr(sums), R, C_, _st(x)),
+                "bn_tok_bwd")
+        zero = torch.zeros_like(mean)
+        L.check(lib.hpfg_bn_tok_apply(L.ptr(dyc), L.ptr(zero), L.ptr(rstd), L.ptr(gamma), L.ptr(zero), L.ptr(dx), R, C_, _st(x)), "bn_tok_apply")
+        return dx, sums[1], sums[0], None, None
+
+
+def batch_norm_tokens_eval(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor, running_var: torch.Tensor,
+                           eps: float = 1e-5) -> torch.Tensor:
+    """Eval-mode BatchNorm over tokens x [..., C]: the affine map of the running statistics, differentiable in x, gamma and beta (the
+    running statistics are constants)."""
+    _need_gpu(x, "batch_norm_tokens_eval")
+    C_ = x.shape[-1]
+    if x.dtype != torch.float32 or x.numel() == 0 or C_ % 4 != 0 or C_ > 1024:
+        raise ValueError(f"batch_norm_tokens_eval: x must be a non-empty float32 [..., C], C a multiple of 4 up to 1024 (got {tuple(x.shape)}, {x.dtype})")
+    if any(tuple(t.shape) != (C_,) for t in (gamma, beta, running_mean, running_var)):
+        raise ValueError(f"batch_norm_tokens_eval: gamma, beta and the running statistics must be [{C_}]")
+    return _BNTokensEval.apply(x, gamma, beta, running_mean.detach(), torch.rsqrt(running_var.detach() + eps))
+
+
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, H, W):

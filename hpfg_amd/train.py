@@ -599,12 +599,13 @@ class HPFGStep(_StepBase):
         from .utils import Dense_Loss
         from .utils.optim import FusedAdamW, flatten_parameters
         from .model.swinunet import SwinUnet_Plus
-        kinds = ["SegFormer_Plus" if isinstance(m, SegFormer_Plus) else "SwinUnet_Plus" if isinstance(m, SwinUnet_Plus) else "U-Net"
-                 for m in (model1, model2, ema_model)]
-        plus = [k != "U-Net" for k in kinds]          # the token-layout networks: three SwinUnet_Plus are handled like three SegFormer_Plus
+        from .model.uniformer import Uniformer_Plus
+        kinds = ["SegFormer_Plus" if isinstance(m, SegFormer_Plus) else "SwinUnet_Plus" if isinstance(m, SwinUnet_Plus) else
+                 "Uniformer_Plus" if isinstance(m, Uniformer_Plus) else "U-Net" for m in (model1, model2, ema_model)]
+        plus = [k != "U-Net" for k in kinds]          # the token-layout networks: three SwinUnet_Plus or Uniformer_Plus are handled like three SegFormer_Plus
         if any(plus):
             if len(set(kinds)) != 1:
-                if "SwinUnet_Plus" in kinds:
+                if "SwinUnet_Plus" in kinds or "Uniformer_Plus" in kinds:
                     raise NotImplementedError(f"HPFGStep: mixed {' / '.join(sorted(set(kinds)))} networks are not built (the three networks must be "
                                               f"of one kind)")
                 raise NotImplementedError("HPFGStep: mixed U-Net / SegFormer_Plus networks are not built (the three networks must be of one kind)")
@@ -614,7 +615,7 @@ class HPFGStep(_StepBase):
                 flatten_parameters(m)
         # SegFormer_Plus draws drop-path factors and the Dropout2d mask from the torch device generator, which hands out its sequence in HOST
         # call order whatever stream the kernels run on: the forwards are then issued as main.py:152-160 calls them -- model1, model2, teacher
-        # (SwinUnet_Plus: its dropout is counter-based, but drop-path still draws from that generator)
+        # (SwinUnet_Plus: its dropout is counter-based, but drop-path still draws from that generator; Uniformer_Plus draws like SegFormer_Plus)
         self.reference_call_order = all(plus)
         super().__init__(args, dp, [model1, model2], ema_model)
         if hasattr(model1, "dense_projection_high"):

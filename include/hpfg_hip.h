@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define HPFG_VERSION 143
+#define HPFG_VERSION 144
 enum { HPFG_MATH_F32 = 0, HPFG_MATH_BF16X3 = 1 };
 
 /* rows of a per-layer BatchNorm table `bn` ([HPFG_BN_ROWS][C] floats) */
@@ -502,6 +502,17 @@ int hpfg_dwgelu_fwd(const float* x, const float* w9, const float* bias, float* y
 int hpfg_dwgelu_bwd(const float* x, const float* w9, const float* bias, const float* dy, float* du /* scratch [B,H,W,C] */, float* dx, float* dw9,
                     float* dbias /* == dw9 + 9*C */, float* partials /* [hpfg_dwgelu_bwd_blocks()][10][C] */, int B, int H, int W, int C, void* stream);
 int hpfg_dwgelu_bwd_blocks(int B, int H, int W);
+/* Depthwise k x k conv (k = 3 or 5, pad k / 2, stride 1) with no activation on [B,H,W,C], C % 4 == 0 (csrc/dwconv.hip; reference model/uniformer.py:
+ * pos_embed, x + dwconv3x3(x), :91,102 and :125,135; CBlock.attn, the depthwise 5 x 5, :96,103).  wk = the [C,1,k,k] weight transposed to [k*k][C].
+ *   fwd: y = (res ? res : 0) + dw_k(x) + bias; res may be x itself.  y is none of the inputs.
+ *   bwd: dx = dw_k^T(dy) (+ dy when add_dy), dwk[t][c] = sum_p dy[p][c] x[p + off(t)][c], dbias[c] = sum_p dy[p][c]; the sums go through one row
+ *        of partials per workgroup and a fixed-order reduction (no atomics: the same bits every run).
+ * Any other k or C returns -1 and launches nothing. */
+int hpfg_dwconv_fwd(const float* x, const float* wk /* [k*k][C] */, const float* bias, const float* res /* NULL or [B,H,W,C]; may be x */, float* y,
+                    int B, int H, int W, int C, int k, void* stream);
+int hpfg_dwconv_bwd(const float* x, const float* wk, const float* dy, float* dx, int add_dy, float* dwk /* [k*k][C] */, float* dbias /* [C] */,
+                    float* partials /* [hpfg_dwconv_bwd_blocks()][k*k+1][C] */, int B, int H, int W, int C, int k, void* stream);
+int hpfg_dwconv_bwd_blocks(int B, int H, int W, int k);
 /* F.interpolate(mode="bilinear", align_corners=False) of SegFormerHead.forward (:314,319) on NHWC [B,h,w,C] -> [B,H,W,C]; backward is a
  * gather over the outputs that tap a source pixel (no atomics), upsampling only */
 int hpfg_resize_bilinear_fwd(const float* x, float* y, int B, int h, int w, int H, int W, int C, void* stream);
@@ -547,6 +558,15 @@ int hpfg_bnrelu_apply(const float* x, const float* mean, const float* rstd, cons
                       long rows_per_image, float* y, long R, int C, void* stream);
 int hpfg_bnrelu_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* mask,
                     float inv_keep, long rows_per_image, float* dx, float* partials, float* sums, long R, int C, void* stream);
+/* Train-mode BatchNorm over tokens x [R][C] with no activation (reference model/uniformer.py: CBlock.norm1 / norm2 :93,97, the stage norms
+ * :292-295), every C % 4 == 0 up to 1024 (320 included, which hpfg_tok_col_stats refuses: the same kernels and, where both admit C, the same bits):
+ *   stats: as hpfg_tok_col_stats, partials [hpfg_tok_stat_blocks(R)][2][C]
+ *   apply: y = (x - mean) * rstd * gamma + beta (eval mode: the running statistics as mean / rstd)
+ *   bwd:   sums[0] = sum_r dy (dbeta), sums[1] = sum_r dy * xhat (dgamma), dx = gamma * rstd * (dy - sums[0] / R - xhat * sums[1] / R) */
+int hpfg_bn_tok_stats(const float* x, long R, int C, float* partials, float* sums /* [2][C] */, void* stream);
+int hpfg_bn_tok_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y, long R, int C, void* stream);
+int hpfg_bn_tok_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma, float* dx,
+                    float* partials /* [hpfg_tok_stat_blocks(R)][2][C] */, float* sums /* [2][C] */, long R, int C, void* stream);
 
 /* ---- parameter updates --------------------------------------------------------------------------------- */
 /* torch.optim.SGD(momentum, weight_decay) over a flat parameter buffer (utils/__init__.py:15-16); lr read from device */
