@@ -83,7 +83,9 @@ __device__ __forceinline__ uint32_t drop_base(const Win& g, int b, int nwin, int
   return (uint32_t)((b * nwin + win) * g.heads + h) * (uint32_t)(g.L() * g.L());
 }
 
-// ds_t of attn_core.h with dP masked before the row sum
+// ds_t of attn_core.h with dP masked before the row sum.  The masked dP is a rounded product of its own (contraction off): fused into the
+// `dp - delta` below, dS would take the unrounded dP .* f while delta summed the rounded one, and a row whose probability sits on one kept
+// key (dS = 0: every other key behind the mask's -100) came out at the product's rounding error, 1e-7 |dP|, instead of 0.
 template <int D>
 __device__ __forceinline__ void ds_drop_t(const unsigned char* ldsV, const bf16x8 (&dh)[Geo<D>::KS], const bf16x8 (&dl)[Geo<D>::KS], int lane,
                                           const f32x4 (&p)[4], const f32x4 (&f)[4], f32x4 (&dp)[4]) {
@@ -93,7 +95,10 @@ __device__ __forceinline__ void ds_drop_t(const unsigned char* ldsV, const bf16x
     tile_t<D>(ldsV, t, dh, dl, lane, dp[t]);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      dp[t][r] *= f[t][r];
+      {
+#pragma clang fp contract(off)
+        dp[t][r] = dp[t][r] * f[t][r];
+      }
       delta += p[t][r] * dp[t][r];
     }
   }

@@ -1342,13 +1342,23 @@ def uncertainty_case(C_, T=8, S=3, Hh=16, W=24):
     return (2.0 * torch.randn(T * S, Hh, W, C_, generator=g)).float()
 
 
-# ---- float64 laws of the attention kernels (csrc/attn.hip, attn_keys.hip, attn_window.hip, the thread-per-query kernels of tokens.hip) --
+# ---- float64 laws of the attention kernels (csrc/attn.hip, attn_keys.hip, attn_window.hip, attn_window_packed.hip, tokens.hip's per-query ones) --
 # One formula, softmax(scale q k^T + bias + mask) v with its closed-form backward, written three times over in plain torch: in float64
 # (the law), in float32 (the yardstick of HPFG_MATH=f32) and in the arithmetic the top of csrc/attn_core.h documents (the yardstick of the
 # split-bf16 kernels).  No tiles, lanes or key blocks.  tests/test_attn_laws_host.py holds the laws against float64 autograd of the
-# written-out formulas and shows that each named mutation is caught; tests/test_gpu_attn_edges.py holds the kernels against the laws.
+# written-out formulas and shows that each named mutation is caught; tests/test_gpu_attn_edges.py holds the kernels against the laws, and
+# tests/test_gpu_attn_window_edges.py the window kernels with a dropout mask and the packed window kernels.
 ATTN_MUTATIONS = ("pad_keys", "dkv_tail", "dk_no_scale")
 WINDOW_MUTATIONS = ("mask_inf", "pad_keys", "bias_transposed", "bias_scaled", "mask_edge", "roll_sign", "hw_swap")
+# of the dropout arithmetic (the DROP kernels of csrc/attn_window.hip and attn_window_packed.hip): f = M (no 1 / (1 - p)); dV from the
+# undropped P; the row sum of dS over the unmasked dP; the mask read as M[l2][l1]
+WINDOW_DROP_MUTATIONS = ("drop_no_rescale", "drop_dv_undropped", "drop_delta_undropped", "drop_transposed")
+# of the packed tile (csrc/attn_window_packed.hip: 64 // w^2 consecutive raster windows of one image share a tile): the keys of the tile's
+# other windows take part with the logit scale q.k (no bias); the mask indexed by the window's slot in its tile, not its index in the image
+PACKED_MUTATIONS = ("tile_leak", "drop_slot_index")
+# what the dQ kernels did until dP .* f became a rounded product of its own (ds_drop_t of csrc/attn_window.h): the compiler fused the product
+# into `dP .* f - delta`, so dS took it unrounded while delta had summed it rounded to float32 -- invisible unless a row's dS is 0
+WINDOW_DROP_ROUNDING = "drop_ds_unrounded"
 ATTN_IMAGE_KEYS = 64             # keys of one LDS image: what a kernel that forgot to exclude the padding keys would normalise over
 ATTN_DKV_QUERIES = 512           # queries per dK / dV workgroup (Q_PER_BLOCK of csrc/attn_core.h)
 WINDOW_MASKED = -100.0           # the reference's literal (model/swinunet.py:204), not -inf
@@ -1370,10 +1380,14 @@ def _prod3(a, b):
     return (ah @ bh + al @ bh + ah @ bl).float()
 
 
-def _attn_core(q, k, v, do, scale, bias=None, mask=None, arith=torch.float64, max_subtract=True, pad_keys=0):
+def _attn_core(q, k, v, do, scale, bias=None, mask=None, arith=torch.float64, max_subtract=True, pad_keys=0, drop=None, mutation=None):
     """q, do [..., Lq, d], k, v [..., Lk, d], bias / mask broadcastable to [..., Lq, Lk] -> out, lse, dq, dk, dv, dS (gradient of the logits).
     arith: torch.float64 / torch.float32 (every operation in that type) or "split" (attn_core.h: scale folded into q, split-bf16 products
-    rounded to float32, float32 softmax, P and dS split again for the second product)."""
+    rounded to float32, float32 softmax, P and dS split again for the second product).
+    drop: the dropout factors f = M / (1 - p) of the probabilities, broadcastable to [..., Lq, Lk] (include/hpfg_hip.h at
+    hpfg_attn_window_drop_fwd): out = (P .* f) V, dP = (dO V^T) .* f, dS = P .* (dP - rowsum(P .* dP)), dV = (P .* f)^T dO; in split
+    arithmetic P .* f is what gets split.  mutation (with drop): "drop_dv_undropped" (dV from P), "drop_delta_undropped" (the row sum over
+    the unmasked dP), "drop_ds_unrounded" (the row sum over dP .* f rounded to float32, dS from the unrounded one)."""
     split = arith == "split"
     dt = torch.float32 if split else arith
     q, k, v, do = (t.to(dt) for t in (q, k, v, do))
@@ -1395,14 +1409,28 @@ def _attn_core(q, k, v, do, scale, bias=None, mask=None, arith=torch.float64, ma
     den = e.sum(-1, keepdim=True)
     P = e * (1.0 / den) if split else e / den
     lse = (mx + torch.log(den)).squeeze(-1)
-    out = mm(P, v)
-    dP = mm(do, T(v))
-    dS = P * (dP - (P * dP).sum(-1, keepdim=True))
+    Pv = P                                         # the probabilities the products with V and dO take
+    if drop is None:
+        out = mm(P, v)
+        dP = mm(do, T(v))
+        dS = P * (dP - (P * dP).sum(-1, keepdim=True))
+    else:
+        f = drop.to(dt)
+        if pad_keys:
+            f = torch.cat([f, torch.ones(*f.shape[:-1], pad_keys, dtype=dt)], -1)
+        Pd = P * f
+        out = mm(Pd, v)
+        raw = mm(do, T(v))
+        dP = raw * f
+        summed = raw if mutation == "drop_delta_undropped" else dP.float().to(dt) if mutation == "drop_ds_unrounded" else dP
+        dS = P * (dP - (P * summed).sum(-1, keepdim=True))
+        if mutation != "drop_dv_undropped":
+            Pv = Pd
     if split:
         dq, dk = mm(dS, k) * torch.tensor(scale, dtype=dt), mm(T(dS), qs)          # dK carries the scale through the scaled q
     else:
         dq, dk = mm(dS, k) * scale, mm(T(dS), q) * scale
-    dv = mm(T(P), do)
+    dv = mm(T(Pv), do)
     if pad_keys:
         dk, dv, dS = dk[..., :-pad_keys, :], dv[..., :-pad_keys, :], dS[..., :-pad_keys]
     return out, lse, dq, dk, dv, dS
@@ -1444,9 +1472,10 @@ def window_reverse(xw, B, H, W, w):
     return xw.reshape(B, H // w, W // w, w, w, C_).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C_)
 
 
-def window_attn_reference(qkv, table, heads, w, s, scale):
+def window_attn_reference(qkv, table, heads, w, s, scale, drop=None):
     """WindowAttention.forward of the reference between its qkv and proj Linear, written out with the reference's own tensor operations
-    (roll, partition, index table, region image, softmax, reverse, roll back); differentiable, any H x W divisible by w."""
+    (roll, partition, index table, region image, softmax, reverse, roll back); differentiable, any H x W divisible by w.
+    drop = (mask, p): attn_drop, the softmax's output times mask / (1 - p) before attn @ v; mask [B nW, heads, L, L]."""
     B, H, W, C3 = qkv.shape
     C_, L_ = C3 // 3, w * w
     d = C_ // heads
@@ -1470,7 +1499,10 @@ def window_attn_reference(qkv, table, heads, w, s, scale):
         m = torch.where(m != 0, torch.full_like(m, WINDOW_MASKED), torch.zeros_like(m))
         nW = m.shape[0]
         a = (a.reshape(B, nW, heads, L_, L_) + m[None, :, None]).reshape(-1, heads, L_, L_)
-    o = (a.softmax(-1) @ v).transpose(1, 2).reshape(-1, L_, C_)
+    a = a.softmax(-1)
+    if drop is not None:
+        a = a * drop[0].to(qkv.dtype) / (1.0 - drop[1])
+    o = (a @ v).transpose(1, 2).reshape(-1, L_, C_)
     o = window_reverse(o, B, H, W, w)
     return torch.roll(o, (s, s), (1, 2)) if s else o
 
@@ -1496,15 +1528,70 @@ def window_tables(H, W, w, s, mutation=None):
     return tok, reg, idx.t() if mutation == "bias_transposed" else idx
 
 
-def window_attn_f64(qkv, table, do, heads, w, s, scale, mutation=None, arith=torch.float64):
+def _drop_factors(drop, B, nW, heads, L_, dt, mutation=None):
+    """drop = (mask uint8 [B nW, heads, L, L], p) -> f = M / (1 - p) as [B, nW, heads, L, L] in dt, with the mutations of the mask's use"""
+    m, p = drop
+    m = m.reshape(B, nW, heads, L_, L_)
+    if mutation == "drop_transposed":
+        m = m.transpose(-2, -1)
+    if mutation == "drop_slot_index":
+        m = m[:, torch.arange(nW) % (ATTN_IMAGE_KEYS // L_)]
+    return m.to(dt) if mutation == "drop_no_rescale" else m.to(dt) / (1.0 - p)
+
+
+def window_attn_tiles_f64(qkv, table, do, heads, w, s, scale, drop=None, mutation=None, arith=torch.float64):
+    """window_attn_f64 in the view of csrc/attn_window_packed.hip: the 64 // w^2 consecutive raster windows of one image that share a tile
+    are one attention over the tile's rows, whose logit between positions of different windows is -inf (the keys are excluded exactly:
+    the law, equal to window_attn_f64) or, with mutation "tile_leak", scale q.k without bias or mask.  Dropout factors between windows are 1."""
+    B, H, W, C3 = qkv.shape
+    C_, L_ = C3 // 3, w * w
+    d = C_ // heads
+    dt = torch.float32 if arith == "split" else arith
+    tok, reg, idx = window_tables(H, W, w, s)
+    nW, per = tok.shape[0], ATTN_IMAGE_KEYS // L_
+    bias = table.to(dt)[idx.reshape(-1)].reshape(L_, L_, heads).permute(2, 0, 1)
+    cross = 0.0 if mutation == "tile_leak" else float("-inf")
+    f_all = None if drop is None else _drop_factors(drop, B, nW, heads, L_, dt, mutation)
+    out, dqkv = torch.zeros(B, H * W, C_, dtype=dt), torch.zeros(B, H * W, 3, heads, d, dtype=dt)
+    dtable = torch.zeros(table.shape[0], heads, dtype=dt)
+    for w0 in range(0, nW, per):
+        n = min(per, nW - w0)
+        tk, R = tok[w0:w0 + n].reshape(-1), n * L_
+        x = qkv.reshape(B, H * W, 3, heads, d)[:, tk].permute(2, 0, 3, 1, 4)                   # [3, B, heads, R, d]
+        dh = do.reshape(B, H * W, heads, d)[:, tk].permute(0, 2, 1, 3)
+        add = torch.full((heads, R, R), cross, dtype=dt)
+        f = None if drop is None else torch.ones(B, heads, R, R, dtype=dt)
+        for i in range(n):
+            own = slice(i * L_, (i + 1) * L_)
+            add[:, own, own] = bias
+            if s:
+                r = reg[w0 + i]
+                add[:, own, own] += torch.where(r[:, None] != r[None, :], WINDOW_MASKED, 0.0).to(dt)
+            if drop is not None:
+                f[:, :, own, own] = f_all[:, w0 + i]
+        o, _, dq, dk, dv, dS = _attn_core(x[0], x[1], x[2], dh, scale, bias=add, arith=arith, drop=f)
+        out[:, tk] = o.permute(0, 2, 1, 3).reshape(B, R, C_)
+        dqkv[:, tk] = torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4)
+        for i in range(n):
+            own = slice(i * L_, (i + 1) * L_)
+            dtable.index_add_(0, idx.reshape(-1), dS[:, :, own, own].sum(0).permute(1, 2, 0).reshape(L_ * L_, heads))
+    return out.reshape(B, H, W, C_), dqkv.reshape(B, H, W, C3), dtable
+
+
+def window_attn_f64(qkv, table, do, heads, w, s, scale, mutation=None, arith=torch.float64, drop=None):
     """Shifted-window attention and its gradients from the index tables: qkv [B,H,W,3 heads d] (channel = t heads d + head d + p),
-    table [(2w-1)^2, heads], do [B,H,W,heads d] -> out like do, dqkv like qkv, dtable like table."""
+    table [(2w-1)^2, heads], do [B,H,W,heads d] -> out like do, dqkv like qkv, dtable like table.
+    drop = (mask, p): dropout of the probabilities, mask uint8 [B nW, heads, L, L] in the element order include/hpfg_hip.h documents for
+    hpfg_attn_window_drop_fwd (the reference's attn tensor in its rolled, window-partitioned order), f = M / (1 - p) as _attn_core states."""
+    if mutation == "tile_leak":
+        return window_attn_tiles_f64(qkv, table, do, heads, w, s, scale, drop, mutation, arith)
     B, H, W, C3 = qkv.shape
     C_, L_ = C3 // 3, w * w
     d = C_ // heads
     dt = torch.float32 if arith == "split" else arith
     tok, reg, idx = window_tables(H, W, w, s, mutation)
     nW = tok.shape[0]
+    f = None if drop is None else _drop_factors(drop, B, nW, heads, L_, dt, mutation)
     x = qkv.reshape(B, H * W, 3, heads, d)[:, tok].permute(3, 0, 1, 4, 2, 5)                  # [3, B, nW, heads, L, d]
     dh = do.reshape(B, H * W, heads, d)[:, tok].permute(0, 1, 3, 2, 4)
     tab = table.to(dt) * (torch.tensor(scale, dtype=dt) if mutation == "bias_scaled" else 1.0)
@@ -1514,7 +1601,7 @@ def window_attn_f64(qkv, table, do, heads, w, s, scale, mutation=None, arith=tor
         differ = reg[:, :, None] != reg[:, None, :]
         mask = torch.where(differ, float("-inf") if mutation == "mask_inf" else WINDOW_MASKED, 0.0).to(dt)[:, None]      # [nW, 1, L, L]
     pad = (-L_) % ATTN_IMAGE_KEYS if mutation == "pad_keys" else 0
-    o, _, dq, dk, dv, dS = _attn_core(x[0], x[1], x[2], dh, scale, bias=bias, mask=mask, arith=arith, pad_keys=pad)
+    o, _, dq, dk, dv, dS = _attn_core(x[0], x[1], x[2], dh, scale, bias=bias, mask=mask, arith=arith, pad_keys=pad, drop=f, mutation=mutation)
     out, dqkv = torch.zeros(B, H * W, C_, dtype=dt), torch.zeros(B, H * W, 3, heads, d, dtype=dt)
     out[:, tok] = o.permute(0, 1, 3, 2, 4).reshape(B, nW, L_, C_)
     dqkv[:, tok] = torch.stack([dq, dk, dv]).permute(1, 2, 4, 0, 3, 5)
@@ -1642,6 +1729,40 @@ def window_case(family, B, H, W, w, s, heads, d, scale=None):
     return dict(qkv=qkv, table=table, do=do, scale=sc, ref=ref, yard=yard, tol=tol)
 
 
+def window_drop_mask(B, nW, heads, L_, p, seed=0):
+    """uint8 [B nW, heads, L, L] of keep rate 1 - p (fixed seed).  In the first window of the first image (head 0) query row 0 has every key
+    dropped (out = 0 and dS = 0 there) and row L - 1 every key kept; a 1 x 1 window has one row, so its kept row is that of the second
+    window.  Both are asserted."""
+    g = torch.Generator().manual_seed(271828 + 7919 * seed + 101 * nW + 13 * L_ + 3 * B + heads + int(1000 * p))
+    m = (torch.rand(B * nW, heads, L_, L_, generator=g) >= p).to(torch.uint8)
+    kept = (0, 0, L_ - 1) if L_ > 1 else (1, 0, 0)
+    m[0, 0, 0] = 0
+    m[kept] = 1
+    assert int(m[0, 0, 0].sum()) == 0 and int(m[kept].sum()) == L_
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def window_drop_case(family, B, H, W, w, s, heads, d, p):
+    """window_case with dropout of the probabilities: the same inputs (so the family's condition is the one window_case asserts), an
+    explicit mask of keep rate 1 - p, and the law, the yardsticks and the tolerances with that mask, by the same attn_tolerance."""
+    c = window_case(family, B, H, W, w, s, heads, d)
+    qkv, table, do, sc = c["qkv"], c["table"], c["do"], c["scale"]
+    mask = window_drop_mask(B, (H // w) * (W // w), heads, w * w, p, seed=1000 * H + 10 * W + s + d)
+    ref = window_results(window_attn_f64(qkv, table, do, heads, w, s, sc, drop=(mask, p)))
+    yard = {m: window_results(window_attn_f64(qkv, table, do, heads, w, s, sc, arith=a, drop=(mask, p))) for m, a in ATTN_YARDSTICK.items()}
+    return dict(qkv=qkv, table=table, do=do, scale=sc, mask=mask, p=p, ref=ref, yard=yard, tol={m: attn_tolerance(ref, y) for m, y in yard.items()})
+
+
+def window_hand_bounds(B, H, W, w, d, math, p=0.0):
+    """The hand constants tests/test_gpu_swin.py, test_gpu_swin_dropout.py and test_gpu_attn_window_packed.py hold the window kernels to
+    (out, dq, dk, dv, dtable), restated for a rectangular map: what tests/test_attn_laws_host.py compares the rule's tolerances with."""
+    k = (1.0 if math == "f32" else 8.0) * (2 ** 0.5 if d == 64 else 1.0)
+    kb = 1.0 if math == "f32" else 8.0
+    pairs = B * (H // w) * (W // w) * w * w
+    return tuple(b / (1.0 - p) for b in (2e-5 * k, 5e-5 * k, 2e-4 * k, 2e-4 * k, 2e-4 * kb * max(1.0, (pairs / 256) ** 0.5)))
+
+
 def worst_ratio(got, ref, tol):
     """max over the tensors of max |got - ref| / tolerance, and the list of the ratios"""
     r = [float((g.double() - x.double()).abs().max()) / t if x.numel() else 0.0 for g, x, t in zip(got, ref, tol)]
@@ -1657,6 +1778,20 @@ ATTN_SCALE_CASES = [(2, 65, 33, 2, 0.3), (2, 65, 33, 2, 0.0)]                   
 # (B, H, W, w, s, heads): 6, 3, 5, 8, 4, 2, 3 and 18 workgroups per head; the first and the last shift; every window size
 WINDOW_EDGES = [(1, 8, 12, 4, 1, 2), (1, 4, 12, 4, 3, 1), (5, 7, 7, 7, 6, 1), (2, 6, 6, 3, 1, 2), (1, 10, 10, 5, 2, 1), (1, 12, 6, 6, 5, 1),
                 (3, 2, 2, 2, 1, 1), (2, 3, 3, 1, 0, 2)]
+# (B, H, W, w, s, heads) of the packed kernels: a tile holds 64 // w^2 = 16 / 7 / 4 windows (slots) of one image in raster order
+PACKED_EDGES = [(1, 2, 2, 2, 0, 1),          # one of 16 slots
+                (1, 8, 8, 2, 1, 1),          # exactly 16 slots
+                (1, 6, 6, 2, 1, 2),          # 9 of 16 slots
+                (2, 8, 10, 2, 1, 1),         # 16 + 4 slots, rectangular, two images: a partial last tile with another image behind it
+                (1, 2, 34, 2, 1, 1),         # 16 + 1 slots
+                (1, 3, 3, 3, 1, 1),          # one of 7 slots; tile row 63 is never live at w = 3
+                (1, 3, 21, 3, 1, 1),         # exactly 7 slots
+                (1, 6, 12, 3, 1, 2),         # 7 + 1 slots
+                (2, 9, 6, 3, 0, 1),          # 6 slots
+                (1, 4, 4, 4, 2, 1),          # window equals map
+                (1, 8, 8, 4, 2, 1),          # exactly 4 slots
+                (1, 4, 20, 4, 2, 1),         # 4 + 1 slots
+                (3, 12, 8, 4, 2, 2)]         # 4 + 2 slots, three images
 WINDOW_HOT = [(1, 14, 14, 7, 3, 1, 32), (1, 8, 12, 4, 1, 1, 32), (1, 8, 8, 4, 3, 1, 64), (1, 16, 16, 8, 7, 1, 32)]      # (.., d): where `hot` was sized
 
 

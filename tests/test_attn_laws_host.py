@@ -1,7 +1,9 @@
 """The float64 laws of the attention kernels (tests/helpers.py: attn_f64, window_attn_f64) against float64 autograd of the written-out
 formulas; the input families' conditions; the yardsticks; and the proof that the rule of tests/test_gpu_attn_edges.py -- error at most
 8 x the yardstick's own error against the law -- would catch each named way of getting the operation wrong: every mutation of the law
-moves some tensor of some case by at least 4 tolerances.  CPU only."""
+moves some tensor of some case by at least 4 tolerances.  The same for the law with a dropout mask and in the packed tile's view, which
+tests/test_gpu_attn_window_edges.py holds the DROP kernels of csrc/attn_window.hip and csrc/attn_window_packed.hip to, and the old hand
+bounds of those kernels beside the rule's tolerances.  CPU only."""
 import pytest
 import torch
 
@@ -174,3 +176,144 @@ def test_emulation_is_the_law_on_operands_bf16_holds_exactly():
     ref, emu = T.attn_f64(q, kv, do, heads, d, 0.125), T.attn_split_emulation(q, kv, do, heads, d, 0.125)
     for a, b in zip(emu, ref):
         assert _rel(a.double(), b) < 2.0 ** -14
+
+
+# ---- dropout of the probabilities and the packed tile (the DROP kernels of csrc/attn_window.hip, all of csrc/attn_window_packed.hip) -------
+P_PACKED, P_WINDOW = 0.1, 0.5
+FAMILIES = ("unit", "sharp", "hot")
+SINGLE_ROW = (2, 3, 3, 1, 0, 2)          # L = 1: dS = 0 and the tolerances are the helper's floor; "written and finite" on the GPU, no mutation counts it
+
+
+def _windows(c):
+    return (c[1] // c[3]) * (c[2] // c[3])
+
+
+def _drop_list(shapes, p):
+    return [(f, *c, d, p) for f in FAMILIES for c in shapes for d in D_ALL]
+
+
+@pytest.mark.parametrize("d", D_ALL)
+@pytest.mark.parametrize("family", ["unit", "hot"])
+@pytest.mark.parametrize("B,H,W,w,s,heads,p", [(*c, P_WINDOW) for c in T.WINDOW_EDGES] + [(*c, P_PACKED) for c in T.PACKED_EDGES])
+def test_dropout_law_is_autograd_of_the_reference_formula_with_the_mask(family, B, H, W, w, s, heads, p, d):
+    c = T.window_drop_case(family, B, H, W, w, s, heads, d, p)
+    qr, tr = c["qkv"].double().requires_grad_(True), c["table"].double().requires_grad_(True)
+    o = T.window_attn_reference(qr, tr, heads, w, s, c["scale"], drop=(c["mask"], p))
+    o.backward(c["do"].double())
+    for name, a, b in zip(T.WINDOW_TENSORS, c["ref"], T.window_results((o.detach(), qr.grad, tr.grad))):
+        assert a.shape == b.shape and _rel(a, b) < 1e-12, name
+    m = c["mask"]
+    assert int(m[0, 0, 0].sum()) == 0          # the forced rows: every key dropped (the law's out row is an exact 0) ...
+    x = c["ref"][0].reshape(B, H, W, heads, d)[0, s % H, s % W, 0]          # ... position 0 of window 0 is the token (s, s)
+    assert float(x.abs().max()) == 0.0
+    assert int(m[(0, 0, w * w - 1) if w > 1 else (1, 0, 0)].sum()) == w * w          # ... and every key kept
+
+
+@pytest.mark.parametrize("d", D_ALL)
+@pytest.mark.parametrize("B,H,W,w,s,heads", T.PACKED_EDGES)
+def test_tile_view_is_the_window_law(B, H, W, w, s, heads, d):
+    """the exclusion between the windows of a tile is exact: the tile view equals the per-window law, without and with a mask"""
+    for family in ("unit", "hot"):
+        c, cd = T.window_case(family, B, H, W, w, s, heads, d), T.window_drop_case(family, B, H, W, w, s, heads, d, P_PACKED)
+        for ref, drop in ((c["ref"], None), (cd["ref"], (cd["mask"], P_PACKED))):
+            tiles = T.window_results(T.window_attn_tiles_f64(c["qkv"], c["table"], c["do"], heads, w, s, c["scale"], drop=drop))
+            for name, a, b in zip(T.WINDOW_TENSORS, tiles, ref):
+                assert _rel(a, b) < 1e-12, (family, name)
+
+
+def _drop_mutant(c, heads, w, s, mutation):
+    return T.window_results(T.window_attn_f64(c["qkv"], c["table"], c["do"], heads, w, s, c["scale"], mutation=mutation, drop=(c["mask"], c["p"])))
+
+
+@pytest.mark.parametrize("mutation", T.WINDOW_DROP_MUTATIONS)
+@pytest.mark.parametrize("which", ["packed", "window"])
+def test_dropout_mutations_are_caught(which, mutation):
+    """f = M, dV from the undropped P, the row sum over the unmasked dP, M[l2][l1]: on PACKED_EDGES at p = 0.1 and on WINDOW_EDGES at p = 0.5"""
+    cases = _drop_list(T.PACKED_EDGES, P_PACKED) if which == "packed" else _drop_list([c for c in T.WINDOW_EDGES if c != SINGLE_ROW], P_WINDOW)
+    best, n_caught = 0.0, 0
+    for family, B, H, W, w, s, heads, d, p in cases:
+        c = T.window_drop_case(family, B, H, W, w, s, heads, d, p)
+        f = _factor(_drop_mutant(c, heads, w, s, mutation), c)
+        print(f"{mutation} p={p} {family} d={d} B={B} H={H} W={W} w={w} s={s} heads={heads}: {f:.3g} tolerances")
+        best, n_caught = max(best, f), n_caught + (f >= 4.0)
+    print(f"{mutation} ({which}, p = {cases[0][-1]}): caught by {n_caught} of {len(cases)} cases, at best {best:.3g} tolerances")
+    assert best >= 4.0
+    if mutation != "drop_transposed":          # (a mask may be symmetric where it matters; the three factors are wrong in every case)
+        assert n_caught == len(cases)
+
+
+def test_unrounded_masked_dp_is_caught_where_a_row_sits_on_one_key():
+    """the mutation of the one kernel fault these cases found (helpers.WINDOW_DROP_ROUNDING): a float32 rounding error of dP .* f left in dS.
+    Beside a dS of ordinary size it is rounding; at (3, 2, 2, 2, 1, 1) every other key of a row is behind the mask's -100, dS = 0 up to
+    e^-100, and the unit and sharp families there must catch it at both head dims"""
+    best, n_caught, n = 0.0, 0, 0
+    for p in (0.1, P_WINDOW):
+        for family, B, H, W, w, s, heads, d, _ in _drop_list([c for c in T.WINDOW_EDGES if c != SINGLE_ROW], p):
+            c = T.window_drop_case(family, B, H, W, w, s, heads, d, p)
+            f = _factor(_drop_mutant(c, heads, w, s, T.WINDOW_DROP_ROUNDING), c)
+            print(f"{T.WINDOW_DROP_ROUNDING} p={p} {family} d={d} B={B} H={H} W={W} w={w} s={s} heads={heads}: {f:.3g} tolerances")
+            best, n_caught, n = max(best, f), n_caught + (f >= 4.0), n + 1
+            if (B, H, W, w, s, heads) == (3, 2, 2, 2, 1, 1) and family != "hot":          # (hot: logits of tens reach over the -100, dS is not 0)
+                assert f >= 4.0, (family, d, p, f)
+    print(f"{T.WINDOW_DROP_ROUNDING}: caught by {n_caught} of {n} cases, at best {best:.3g} tolerances")
+    assert best >= 4.0
+
+
+@pytest.mark.parametrize("drop", [False, True])
+@pytest.mark.parametrize("mutation", T.PACKED_MUTATIONS)
+def test_packed_mutations_are_caught(mutation, drop):
+    """tile_leak: every case whose image has more than one window; drop_slot_index: every case whose image has more than one tile"""
+    if mutation == "drop_slot_index" and not drop:
+        return          # (no mask, nothing to index)
+    best, n_caught, n_must, cases = 0.0, 0, 0, [(f, *c, d) for f in FAMILIES for c in T.PACKED_EDGES for d in D_ALL]
+    for family, B, H, W, w, s, heads, d in cases:
+        c = T.window_drop_case(family, B, H, W, w, s, heads, d, P_PACKED) if drop else T.window_case(family, B, H, W, w, s, heads, d)
+        dr = (c["mask"], P_PACKED) if drop else None
+        f = _factor(T.window_results(T.window_attn_f64(c["qkv"], c["table"], c["do"], heads, w, s, c["scale"], mutation=mutation, drop=dr)), c)
+        print(f"{mutation} drop={drop} {family} d={d} B={B} H={H} W={W} w={w} s={s} heads={heads}: {f:.3g} tolerances")
+        best, n_caught = max(best, f), n_caught + (f >= 4.0)
+        nW = _windows((B, H, W, w))
+        if nW > (1 if mutation == "tile_leak" else T.ATTN_IMAGE_KEYS // (w * w)):
+            n_must += 1
+            assert f >= 4.0, (mutation, family, B, H, W, w, s, heads, d, f)
+        elif mutation == "tile_leak":
+            assert f < 1e-9          # one window: nothing to leak (the float64 sums in another order)
+    print(f"{mutation} (dropout mask: {drop}): caught by {n_caught} of {len(cases)} cases ({n_must} have more than one "
+          f"{'window' if mutation == 'tile_leak' else 'tile'}), at best {best:.3g} tolerances")
+    assert best >= 4.0 and n_caught >= n_must > 0
+
+
+def test_packed_mask_literal_needs_the_hot_family():
+    """the packed kernel writes NEG for another window's keys before the maximum, beside the shift mask's literal -100: on unit logits -inf
+    for -100 moves nothing, on the hot family `out` moves by hundreds of tolerances at every shifted packed shape"""
+    least = float("inf")
+    for B, H, W, w, s, heads in T.PACKED_EDGES:
+        if not s:
+            continue
+        for d in D_ALL:
+            c = T.window_case("unit", B, H, W, w, s, heads, d)
+            mut = T.window_attn_f64(c["qkv"], c["table"], c["do"], heads, w, s, c["scale"], mutation="mask_inf")
+            assert float((mut[0] - c["ref"][0]).abs().max()) == 0.0
+            c = T.window_case("hot", B, H, W, w, s, heads, d)
+            mut = T.window_attn_f64(c["qkv"], c["table"], c["do"], heads, w, s, c["scale"], mutation="mask_inf")
+            f = min(T.worst_ratio(mut[:1], c["ref"][:1], c["tol"][m][:1])[0] for m in T.ATTN_MATHS)
+            print(f"mask_inf hot d={d} B={B} H={H} W={W} w={w} s={s} heads={heads}: out moves by {f:.3g} tolerances")
+            least = min(least, f)
+    assert least >= 4.0
+
+
+@pytest.mark.parametrize("d", D_ALL)
+def test_the_rule_is_no_looser_than_the_hand_bounds(d):
+    """The packed and dropout GPU files so far hold the kernels to hand constants (helpers.window_hand_bounds).  Per tensor, hand bound /
+    rule's tolerance on PACKED_EDGES (unit, bf16x3), without and with the mask: the hand bound is never the tighter one by more than 2 x,
+    so holding the kernels to the rule weakens nothing -- and is up to tens of times tighter for the gradients."""
+    for p in (0.0, P_PACKED):
+        lo, hi = [float("inf")] * 5, [0.0] * 5
+        for B, H, W, w, s, heads in T.PACKED_EDGES:
+            c = T.window_drop_case("unit", B, H, W, w, s, heads, d, p) if p else T.window_case("unit", B, H, W, w, s, heads, d)
+            r = [h / t for h, t in zip(T.window_hand_bounds(B, H, W, w, d, "bf16x3", p), c["tol"]["bf16x3"])]
+            print(f"d={d} p={p} B={B} H={H} W={W} w={w} s={s} heads={heads}: hand bound / tolerance  " +
+                  "  ".join(f"{n} {x:.2f}" for n, x in zip(T.WINDOW_TENSORS, r)))
+            lo, hi = [min(a, x) for a, x in zip(lo, r)], [max(a, x) for a, x in zip(hi, r)]
+        print(f"d={d} p={p}: " + "  ".join(f"{n} {a:.2f} .. {b:.2f}" for n, a, b in zip(T.WINDOW_TENSORS, lo, hi)))
+        assert min(lo) >= 0.5, lo

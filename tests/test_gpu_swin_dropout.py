@@ -15,6 +15,7 @@ from hpfg_amd.ops_tokens import (dropout_mask, token_dropout, window_attention, 
                                  window_attention_mask_elems)
 from tests import helpers_swinunet as S
 from tests import test_gpu_swin as SW
+from tests.helpers import window_attn_reference
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -25,32 +26,9 @@ STRIDE_CAP = 8192 * 256          # float4 items of one pass of the grid-stride k
 
 
 def _reference(qkv, table, mask, p, heads, w, s, scale):
-    """SW._reference with attn_drop: the softmax's output times mask / (1 - p) before attn @ v; mask [B nW, heads, L, L]."""
-    B, H, W, C3 = qkv.shape
-    C_, L_ = C3 // 3, w * w
-    d = C_ // heads
-    x = torch.roll(qkv, (-s, -s), (1, 2)) if s else qkv
-    xw = SW._partition(x, w).reshape(-1, L_, 3, heads, d).permute(2, 0, 3, 1, 4)
-    q, k, v = xw[0] * scale, xw[1], xw[2]
-    a = q @ k.transpose(-2, -1)
-    l = torch.arange(L_)
-    i, j = l // w, l % w
-    idx = (i[:, None] - i[None, :] + w - 1) * (2 * w - 1) + (j[:, None] - j[None, :] + w - 1)
-    a = a + table[idx.reshape(-1)].reshape(L_, L_, heads).permute(2, 0, 1)[None]
-    if s:
-        img = torch.zeros(1, H, W, 1, dtype=qkv.dtype)
-        cnt = 0
-        for hs in (slice(0, -w), slice(-w, -s), slice(-s, None)):
-            for ws in (slice(0, -w), slice(-w, -s), slice(-s, None)):
-                img[:, hs, ws, :] = cnt
-                cnt += 1
-        mw = SW._partition(img, w).reshape(-1, L_)
-        m = mw[:, None, :] - mw[:, :, None]
-        m = torch.where(m != 0, torch.full_like(m, -100.0), torch.zeros_like(m))
-        a = (a.reshape(B, m.shape[0], heads, L_, L_) + m[None, :, None]).reshape(-1, heads, L_, L_)
-    a = a.softmax(-1) * mask.to(qkv.dtype) / (1.0 - p)
-    o = SW._reverse((a @ v).transpose(1, 2).reshape(-1, L_, C_), B, H, W, w)
-    return torch.roll(o, (s, s), (1, 2)) if s else o
+    """SW._reference with attn_drop: the softmax's output times mask / (1 - p) before attn @ v; mask [B nW, heads, L, L].  The formula is
+    the drop argument of tests/helpers.window_attn_reference."""
+    return window_attn_reference(qkv, table, heads, w, s, scale, drop=(mask, p))
 
 
 @functools.lru_cache(maxsize=None)

@@ -17,8 +17,8 @@ the C entry points:
 each attention case at head dims 32 and 64.  Writes one JSON object {case: {result: digest}} to --out.
 
 To compare two trees, run this same file in each (a fresh process per tree) and compare the two JSON files; tests/golden/dense_bits.json
-is the run of the commit before the arithmetic moved into csrc/bf16x3.h, and tests/test_gpu_dense_bits.py compares against it.  Needs a
-GPU: there is no fallback."""
+is the run of the commit before the arithmetic moved into csrc/bf16x3.h (but for the dqkv / dtable digests of the window drop cases, see
+the test's docstring), and tests/test_gpu_dense_bits.py compares against it.  Needs a GPU: there is no fallback."""
 import argparse
 import hashlib
 import json
